@@ -249,6 +249,38 @@ def cpu_baseline(k: int, cores: int, K: int = 0, target_s: float = 20.0):
     return {"value": kmers / wall / 1e6, "unit": "Mk-mers/s", "cores": 1, "kind": "port", "sample": sample}
 
 
+DUMP_SAMPLE = 1 << 22  # positions of each filter sampled by --dump-outputs (4 Mi x float32 = 16 MB per filter)
+
+
+def dump_outputs(g, rank: int, out_dir: str):
+    """--dump-outputs: what the timed path leaves its caller after its last step, as float arrays in `out_dir` (rank 0 writes).
+    The timed path keeps its unitigs on the device and hands back the assembly counters (unitig count and length among them);
+    what it computed besides is the counting filter and the visited filter, dumped as their popcounts, the histogram of the
+    counter values and the values at DUMP_SAMPLE positions drawn with a fixed seed (the same positions for the same filter size).
+    Every rank makes the calls: on a sliced filter the exports are collectives (include/abyss_amd.h, abg_attach_comm)."""
+    arrays = {}
+    c = g.assembly_counters()
+    arrays["assembly_counters"] = np.array([c[n] for n in ("solid_reads", "visited_reads", "reads_processed", "bases_assembled",
+                                                           "next_contig_id")], dtype=np.float64)
+    arrays["counting_popcount"] = np.array(g.counting_stats(), dtype=np.float64)
+    rng = np.random.default_rng(20261015)
+    if g.size <= (4 << 30):  # (a counter array of tens of GB is not copied to the host for this)
+        cnt = g.counters()
+        arrays["counters_histogram"] = np.bincount(cnt, minlength=256).astype(np.float64)
+        arrays["counters_sample"] = cnt[np.sort(rng.integers(0, cnt.size, DUMP_SAMPLE))].astype(np.float32)
+        del cnt
+    vis = g.visited()
+    bits = np.array([bin(i).count("1") for i in range(256)], dtype=np.uint8)
+    arrays["visited_popcount"] = np.array([bits[vis].sum(dtype=np.uint64)], dtype=np.float64)
+    arrays["visited_sample"] = vis[np.sort(rng.integers(0, vis.size, DUMP_SAMPLE))].astype(np.float32)
+    del vis
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, arr in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return sorted(arrays)
+
+
 def aggregate(elapsed: float, kmers_local: int, steps: int, world: int, device=None):
     """Whole-job numbers from per-rank ones: time = MAX over ranks of the timed region, units =
     SUM over ranks (every rank processes its own read set).  Returns (seconds, total k-mers)."""
@@ -289,6 +321,9 @@ def main() -> int:
                     help="after the timed steps, add digests of the last step's device state to the line (popcounts of the counting filter, "
                          "sha256 of the counting and the visited filter, read and unitig counters): what two runs of one workload -- "
                          "e.g. plain and ABG_FORCE_DIST=1 -- must agree on where no reference run exists (configs[2])")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64, "
+                         "under 64 MB in all): see dump_outputs()")
     ap.add_argument("--no-events", action="store_true",
                     help="time the steps without HIP events around every launch (no per-kernel numbers: shows what the events cost)")
     ap.add_argument("--mode", choices=["partitioned", "replicas"], default="partitioned",
@@ -532,6 +567,7 @@ def main() -> int:
         step(profile=timed_profile and not a.no_events)
     barrier()
     elapsed = time.perf_counter() - t0
+    dumped = dump_outputs(g, rank, a.dump_outputs) if (a.dump_outputs and g is not None) else None
     # per-kernel HIP-event timings of the last timed step (events are recorded on the library's stream)
     if prof is None:
         prof = {nm: g.profile_get(nm) for nm in names}
@@ -676,6 +712,8 @@ def main() -> int:
         }
         if parity is not None:
             out["parity"] = parity
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
         if no_events is not None:
             out["no_events"] = no_events
         if selftest is not None:

@@ -2,18 +2,19 @@
 
 The reference's pipeline driver is a Makefile (bin/abyss-pe); with `B=` set its `%-1.fa` rule is
 `abyss-stack-size 65536 abyss-bloom-dbg $(abyssopt) $(in) $(se) > $@` (bin/abyss-pe:553-555,
-191-235).  Two halves, because the reference tree exists only in the build container and a GPU
-only on the GPU box:
+191-235).  Two halves:
 
-* here (no GPU, reference present): the unmodified abyss-pe is run with OUR binary first on PATH,
-  wrapped by a recorder; the recorded command line is the one the GPU tests feed the binary
+* the command lines the unmodified abyss-pe issues for its rules, recorded once from the reference
+  (tests/golden/abyss_pe_rules.json, made by tests/golden/make_abyss_pe.py), are fed to OUR binaries:
+  the recorded command line is the one the GPU tests feed the binary
   (tests/test_gpu_cli.py::test_cli_matches_reference_binary_on_fastq), our option parser accepts
-  it (the run ends at "no HIP device", not at an option error), and the one-letter `name=` trap of
-  SURVEY.md 8c (`name=t` injects `-t<files>`) is what it is;
-* on the GPU box (`-m gpu`, no reference tree): a stand-in for that one rule -- the same command
-  through an `abyss-stack-size` wrapper raising the stack limit -- writes the same `asm-1.fa` as
-  the direct invocation.
+  it (without a GPU the run ends at "no HIP device", not at an option error), and the one-letter
+  `name=` trap of SURVEY.md 8c (`name=t` injects `-t<files>`) is what it is;
+* on the GPU box (`-m gpu`): a stand-in for that one rule -- the same command through an
+  `abyss-stack-size` wrapper raising the stack limit -- writes the same `asm-1.fa` as the direct
+  invocation.
 """
+import json
 import os
 import stat
 import subprocess
@@ -22,7 +23,8 @@ import pytest
 
 from abyss_amd import build, synth
 
-REF_PE = "/root/reference/bin/abyss-pe"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+RULES = json.load(open(os.path.join(GOLDEN, "abyss_pe_rules.json")))
 
 
 def _write_reads(tmp_path, genome=20000, cov=10.0):
@@ -31,41 +33,38 @@ def _write_reads(tmp_path, genome=20000, cov=10.0):
     synth.write_fastq(str(tmp_path / "r2.fq"), m2, "r", 2)
 
 
-def _shim_dir(tmp_path, real):
-    d = tmp_path / "shim"
-    d.mkdir()
-    rec = tmp_path / "argv.txt"
-    sh = d / "abyss-bloom-dbg"
-    sh.write_text("#!/bin/sh\nprintf '%%s\\n' \"$@\" > %s\nexec %s \"$@\"\n" % (rec, real))
-    sh.chmod(sh.stat().st_mode | stat.S_IXUSR)
-    return d, rec
-
-
-@pytest.mark.skipif(not os.path.exists(REF_PE), reason="the reference tree is not on this machine")
-def test_abyss_pe_issues_the_command_line_our_binary_accepts(tmp_path):
-    cli = build.build_cli()
-    _write_reads(tmp_path)
-    shim, rec = _shim_dir(tmp_path, cli)
-    env = dict(os.environ, PATH="%s:%s" % (shim, os.environ["PATH"]))
-    r = subprocess.run(["make", "-rRf", REF_PE, "name=asm", "k=32", "B=100M", "j=1", "in=r1.fq r2.fq", "asm-1.fa"],
-                       cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
-    out = (r.stdout + r.stderr).decode()
-    assert "abyss-stack-size 65536 abyss-bloom-dbg -k32 -q3" in out, out
-    assert rec.read_text().split("\n")[:-1] == ["-k32", "-q3", "-b100M", "-j1", "r1.fq", "r2.fq"]
+def _have_gpu():
     try:
         import torch
-        have_gpu = torch.cuda.is_available()
+        return torch.cuda.is_available()
     except Exception:  # noqa: BLE001
-        have_gpu = False
-    if have_gpu:
-        assert r.returncode == 0 and (tmp_path / "asm-1.fa").read_bytes().startswith(b">0 ")
+        return False
+
+
+def _replay(tmp_path, rule):
+    """Our binary of a recorded rule, with the argv abyss-pe gave it, in tmp_path: (returncode, stdout, stdout + stderr)."""
+    exe = os.path.join(build.BIN_DIR, RULES[rule]["binary"])
+    r = subprocess.run([exe] + RULES[rule]["argv"], cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    return r.returncode, r.stdout, (r.stdout + r.stderr).decode()
+
+
+def test_abyss_pe_issues_the_command_line_our_binary_accepts(tmp_path):
+    build.build_cli()
+    _write_reads(tmp_path)
+    rule = RULES["unitigs"]
+    assert rule["make_args"] == ["name=asm", "k=32", "B=100M", "j=1", "in=r1.fq r2.fq", "asm-1.fa"]
+    assert "abyss-stack-size 65536 abyss-bloom-dbg -k32 -q3" in rule["recipe"], rule["recipe"]
+    assert rule["argv"] == ["-k32", "-q3", "-b100M", "-j1", "r1.fq", "r2.fq"]
+    rc, stdout, out = _replay(tmp_path, "unitigs")
+    if _have_gpu():
+        assert rc == 0 and stdout.startswith(b">0 "), out
     else:
         # the options were accepted and the inputs opened; what stops the run is the missing device
-        assert r.returncode != 0 and "no HIP device" in out and "invalid option" not in out and "missing" not in out, out
+        assert rc != 0 and "no HIP device" in out and "invalid option" not in out and "missing" not in out, out
     # the one-letter trap: `name=t` makes $(t) the input files, which abyss-pe turns into `-t<files>`
-    r = subprocess.run(["make", "-rRf", REF_PE, "name=t", "k=32", "B=100M", "j=1", "in=r1.fq r2.fq", "t-1.fa"],
-                       cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
-    assert any(a.startswith("-t") and "r1.fq" in a for a in rec.read_text().split("\n")), rec.read_text()
+    trap = RULES["unitigs_name_t"]
+    assert trap["make_args"][0] == "name=t" and trap["make_args"][-1] == "t-1.fa"
+    assert any(a.startswith("-t") and "r1.fq" in a for a in trap["argv"]), trap["argv"]
 
 
 @pytest.mark.gpu
@@ -85,38 +84,23 @@ def test_pipeline_rule_writes_the_same_file_as_the_direct_call(tmp_path):
     assert (tmp_path / "asm-1.fa").read_bytes() == direct.stdout and direct.stdout.count(b">") > 300
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PE), reason="the reference tree is not on this machine")
 @pytest.mark.parametrize("k,extra,want", [(32, [], ["-k32", "-m0", "--dot", "asm-1.fa"]),
                                            (64, ["SS=--SS"], ["--SS", "-k64", "-m50", "--dot", "asm-1.fa"]),
                                            (96, ["v=-v", "graph=gfa2"], ["-v", "-k96", "-m50", "--gfa2", "asm-1.fa"])])
 def test_abyss_pe_issues_the_adjlist_command_line_our_binary_accepts(tmp_path, k, extra, want):
     """The step after `-1.fa` (bin/abyss-pe:238-246,575-577): `AdjList $(alopt) --$g asm-1.fa >asm-1.$g`."""
+    rule = {32: "adjlist_k32", 64: "adjlist_k64_ss", 96: "adjlist_k96_gfa2"}[k]
     build.build_cli()
-    real = os.path.join(build.BIN_DIR, "AdjList")
-    d = tmp_path / "shim"
-    d.mkdir()
-    rec = tmp_path / "argv.txt"
-    sh = d / "AdjList"
-    sh.write_text("#!/bin/sh\nprintf '%%s\\n' \"$@\" > %s\nexec %s \"$@\"\n" % (rec, real))
-    sh.chmod(sh.stat().st_mode | stat.S_IXUSR)
-    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "k%d.fa" % k)
+    golden = os.path.join(GOLDEN, "k%d.fa" % k)
     (tmp_path / "asm-1.fa").write_bytes(open(golden, "rb").read())
     g = "gfa2" if "graph=gfa2" in extra else "dot"
-    env = dict(os.environ, PATH="%s:%s" % (d, os.environ["PATH"]))
-    r = subprocess.run(["make", "-rRf", REF_PE, "name=asm", "k=%d" % k, "B=100M", "j=1", "in=r1.fq r2.fq"] + extra + ["asm-1.%s" % g],
-                       cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
-    out = (r.stdout + r.stderr).decode()
-    assert rec.exists(), out
-    assert rec.read_text().split("\n")[:-1] == want
-    try:
-        import torch
-        have_gpu = torch.cuda.is_available()
-    except Exception:  # noqa: BLE001
-        have_gpu = False
-    if have_gpu:
-        assert r.returncode == 0, out
+    assert RULES[rule]["make_args"] == ["name=asm", "k=%d" % k, "B=100M", "j=1", "in=r1.fq r2.fq"] + extra + ["asm-1.%s" % g]
+    assert RULES[rule]["binary"] == "AdjList" and RULES[rule]["argv"] == want
+    rc, _, out = _replay(tmp_path, rule)
+    if _have_gpu():
+        assert rc == 0, out
     else:
-        assert r.returncode != 0 and "no HIP device" in out and "invalid option" not in out, out
+        assert rc != 0 and "no HIP device" in out and "invalid option" not in out, out
 
 
 @pytest.mark.gpu
@@ -142,39 +126,24 @@ def test_the_two_rules_in_a_row_write_the_reference_overlap_graph(tmp_path):
         assert r.returncode == 0 and r.stdout == (tmp_path / "asm-1.dot").read_bytes()
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PE), reason="the reference tree is not on this machine")
 def test_abyss_pe_issues_the_rresolver_command_line_our_binary_accepts(tmp_path):
     """The rule after `-1.dot` in Bloom mode (bin/abyss-pe:581-585): `abyss-rresolver-short -b$B -f0.8 -j$j -k$k -h asm-1-rr --dot
     -c asm-1-rr.fa -g asm-1-rr.dot asm-1.fa asm-1.dot $(in)`."""
     import rr_util
     build.build_cli()
-    real = os.path.join(build.BIN_DIR, "abyss-rresolver-short")
-    d = tmp_path / "shim"
-    d.mkdir()
-    rec = tmp_path / "argv.txt"
-    sh = d / "abyss-rresolver-short"
-    sh.write_text("#!/bin/sh\nprintf '%%s\\n' \"$@\" > %s\nexec %s \"$@\"\n" % (rec, real))
-    sh.chmod(sh.stat().st_mode | stat.S_IXUSR)
     reads = rr_util.write_inputs(str(tmp_path), "rr_k32")
     os.rename(tmp_path / "rr_k32-1.fa", tmp_path / "asm-1.fa")
     os.rename(tmp_path / "rr_k32-1.dot", tmp_path / "asm-1.dot")
-    env = dict(os.environ, PATH="%s:%s" % (d, os.environ["PATH"]))
-    r = subprocess.run(["make", "-rRf", REF_PE, "name=asm", "k=32", "B=8M", "j=2", "in=%s" % " ".join(reads), "asm-1-rr.fa"],
-                       cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
-    out = (r.stdout + r.stderr).decode()
-    assert rec.exists(), out
-    assert rec.read_text().split("\n")[:-1] == ["-b8M", "-f0.8", "-j2", "-k32", "-h", "asm-1-rr", "--dot", "-c", "asm-1-rr.fa", "-g", "asm-1-rr.dot",
-                                                 "asm-1.fa", "asm-1.dot"] + reads
-    try:
-        import torch
-        have_gpu = torch.cuda.is_available()
-    except Exception:  # noqa: BLE001
-        have_gpu = False
-    if have_gpu:
-        assert r.returncode == 0, out
+    rule = RULES["rresolver"]
+    assert rule["make_args"] == ["name=asm", "k=32", "B=8M", "j=2", "in=%s" % " ".join(reads), "asm-1-rr.fa"]
+    assert rule["argv"] == ["-b8M", "-f0.8", "-j2", "-k32", "-h", "asm-1-rr", "--dot", "-c", "asm-1-rr.fa", "-g", "asm-1-rr.dot",
+                            "asm-1.fa", "asm-1.dot"] + reads
+    rc, _, out = _replay(tmp_path, "rresolver")
+    if _have_gpu():
+        assert rc == 0, out
         assert (tmp_path / "asm-1-rr.fa").read_bytes() == rr_util.golden_outputs("rr_k32")["rr_k32-1-rr.fa"]
     else:
-        assert r.returncode != 0 and "no HIP device" in out and "invalid option" not in out and "missing" not in out, out
+        assert rc != 0 and "no HIP device" in out and "invalid option" not in out and "missing" not in out, out
 
 
 @pytest.mark.gpu

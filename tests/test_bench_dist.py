@@ -79,3 +79,49 @@ def test_evidence_is_tied_to_the_kernel_sources(tmp_path, monkeypatch):
     path, j, head, behind = bench.pick_evidence("_pmc_traffic.json")
     assert path.endswith("r02_pmc_traffic.json") and not head and behind is None
     assert bench.pick_evidence("_nothing.json") == (None, None, False, None)
+
+
+def test_dump_outputs_writes_float_arrays_of_the_last_step(tmp_path):
+    """--dump-outputs: every array float32 / float64, 64 MB at most, the same bytes for the same filters."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+
+    class FakeEngine:
+        size = 1 << 24
+
+        def __init__(self):
+            rng = np.random.default_rng(3)
+            self._cnt = rng.integers(0, 4, self.size, dtype=np.uint8)
+            self._vis = rng.integers(0, 256, self.size // 8, dtype=np.uint8)
+
+        def assembly_counters(self):
+            return {"solid_reads": 10, "visited_reads": 9, "reads_processed": 12, "bases_assembled": 4321, "next_contig_id": 17}
+
+        def counting_stats(self):
+            return int(np.count_nonzero(self._cnt)), int(np.count_nonzero(self._cnt >= 2))
+
+        def counters(self):
+            return self._cnt.copy()
+
+        def visited(self):
+            return self._vis.copy()
+
+    g = FakeEngine()
+    names = bench.dump_outputs(g, 0, str(tmp_path / "a"))
+    bench.dump_outputs(g, 0, str(tmp_path / "b"))
+    assert bench.dump_outputs(g, 1, str(tmp_path / "c")) == names and not (tmp_path / "c").exists()  # only rank 0 writes
+    assert sorted(f[:-4] for f in os.listdir(tmp_path / "a")) == names
+    total = 0
+    for n in names:
+        arr = np.load(tmp_path / "a" / (n + ".npy"))
+        assert arr.dtype in (np.float32, np.float64)
+        assert (tmp_path / "a" / (n + ".npy")).read_bytes() == (tmp_path / "b" / (n + ".npy")).read_bytes()
+        total += os.path.getsize(tmp_path / "a" / (n + ".npy"))
+    assert total <= 64 << 20
+    ac = np.load(tmp_path / "a" / "assembly_counters.npy")
+    assert list(ac) == [10, 9, 12, 4321, 17]
+    assert list(np.load(tmp_path / "a" / "counting_popcount.npy")) == list(g.counting_stats())
+    assert np.load(tmp_path / "a" / "counters_histogram.npy").sum() == g.size
+    assert np.load(tmp_path / "a" / "visited_popcount.npy")[0] == np.unpackbits(g._vis).sum()
+    assert set(np.unique(np.load(tmp_path / "a" / "counters_sample.npy"))) <= {0, 1, 2, 3}
