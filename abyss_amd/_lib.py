@@ -61,6 +61,8 @@ def symbols():
         "abg_overlap_profile", "abg_overlap_profile_get",
         "abg_rr_create", "abg_rr_destroy", "abg_rr_last_error", "abg_rr_bytes", "abg_rr_clear", "abg_rr_insert_seqs",
         "abg_rr_contains_seqs", "abg_rr_popcount", "abg_rr_export", "abg_rr_sync", "abg_rr_profile", "abg_rr_profile_get",
+        "abg_kn_create", "abg_kn_destroy", "abg_kn_last_error", "abg_kn_import", "abg_kn_export", "abg_kn_insert_seqs",
+        "abg_kn_contains_seqs", "abg_kn_popcount", "abg_kn_hash_seq", "abg_kn_sync", "abg_kn_profile", "abg_kn_profile_get",
     ]
 
 
@@ -138,5 +140,19 @@ def load(path: str | None = None):
     lib.abg_rr_sync.argtypes = [vp]
     lib.abg_rr_profile.argtypes = [vp, C.c_int]
     lib.abg_rr_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
+    lib.abg_kn_create.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(vp)]
+    lib.abg_kn_destroy.argtypes = [vp]
+    lib.abg_kn_destroy.restype = None
+    lib.abg_kn_last_error.argtypes = [vp]
+    lib.abg_kn_last_error.restype = C.c_char_p
+    lib.abg_kn_import.argtypes = [vp, C.c_uint32, vp]
+    lib.abg_kn_export.argtypes = [vp, C.c_uint32, vp]
+    lib.abg_kn_insert_seqs.argtypes = [vp, vp, vp, C.c_uint64]
+    lib.abg_kn_contains_seqs.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, vp]
+    lib.abg_kn_popcount.argtypes = [vp, vp]
+    lib.abg_kn_hash_seq.argtypes = [vp, C.c_char_p, C.c_uint64, vp, vp, vp]
+    lib.abg_kn_sync.argtypes = [vp]
+    lib.abg_kn_profile.argtypes = [vp, C.c_int]
+    lib.abg_kn_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
     _lib = lib
     return lib

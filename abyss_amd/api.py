@@ -517,3 +517,92 @@ class ReadFilter:
         ms, n = C.c_double(), C.c_uint64()
         self._lib.abg_rr_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
         return ms.value, n.value
+
+
+class KonnectorBloom:
+    """A Konnector Bloom filter on one GPU: `abyss-bloom build -t konnector` (Bloom/BloomFilter.h, CascadingBloomFilter.h,
+    BloomFilterWindow.h; include/abyss_amd.h abg_kn_*).  `bits` is the index space (hash % bits); the filter holds `levels`
+    levels of its window [start, end] (the whole space by default)."""
+
+    def __init__(self, k: int, bits: int, levels: int = 1, seed: int = 0, start: int = 0, end: int = None, device: int = 0):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        self.k, self.bits, self.levels, self.seed = k, bits, levels, seed
+        self.start, self.end = start, bits - 1 if end is None else end
+        rc = self._lib.abg_kn_create(device, bits, levels, k, seed, self.start, self.end, C.byref(self._h))
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_kn_last_error(None)
+            self._h = None
+            raise AbyssAmdError("abg_kn_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.abg_kn_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_kn_last_error(self._h)
+            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+
+    @property
+    def level_bytes(self) -> int:
+        return (self.end - self.start + 1 + 7) // 8
+
+    def load(self, buf: bytes, off: np.ndarray) -> None:
+        """Bloom::loadSeq for every sequence (ASCII + offsets)."""
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        keep = C.c_char_p(buf)
+        self._check(self._lib.abg_kn_insert_seqs(self._h, C.cast(keep, C.c_void_p), off.ctypes.data, len(off) - 1), "abg_kn_insert_seqs")
+        self._check(self._lib.abg_kn_sync(self._h), "abg_kn_sync")
+
+    def contains(self, buf: bytes, off: np.ndarray, inverse: bool = False) -> np.ndarray:
+        """One flag per position of buf: the window starting there is all ACGT and (in level 0) != inverse."""
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        out = np.zeros(max(1, int(off[-1] - off[0])), dtype=np.uint8)
+        keep = C.c_char_p(buf)
+        self._check(self._lib.abg_kn_contains_seqs(self._h, C.cast(keep, C.c_void_p), off.ctypes.data, len(off) - 1, int(inverse),
+                                                   out.ctypes.data), "abg_kn_contains_seqs")
+        return out[:int(off[-1] - off[0])]
+
+    def hash_seq(self, seq: bytes) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(hash, index, valid) of every window of seq."""
+        n = max(0, len(seq) - self.k + 1)
+        h, i, v = np.zeros(max(1, n), np.uint64), np.zeros(max(1, n), np.uint64), np.zeros(max(1, n), np.uint8)
+        self._check(self._lib.abg_kn_hash_seq(self._h, seq, len(seq), h.ctypes.data, i.ctypes.data, v.ctypes.data), "abg_kn_hash_seq")
+        return h[:n], i[:n], v[:n].astype(bool)
+
+    def popcount(self) -> List[int]:
+        out = np.zeros(self.levels, dtype=np.uint64)
+        self._check(self._lib.abg_kn_popcount(self._h, out.ctypes.data), "abg_kn_popcount")
+        return [int(x) for x in out]
+
+    def level(self, level: int) -> np.ndarray:
+        out = np.zeros(self.level_bytes, dtype=np.uint8)
+        self._check(self._lib.abg_kn_export(self._h, level, out.ctypes.data), "abg_kn_export")
+        return out
+
+    def set_level(self, level: int, arr: np.ndarray) -> None:
+        arr = np.ascontiguousarray(arr, dtype=np.uint8)
+        if arr.size != self.level_bytes:
+            raise ValueError("a level is %d bytes" % self.level_bytes)
+        self._check(self._lib.abg_kn_import(self._h, level, arr.ctypes.data), "abg_kn_import")
+
+    def file(self) -> bytes:
+        """The filter file of the last level (Bloom::writeHeader + the window's bytes)."""
+        head = b"5\n%d\n%d\t%d\t%d\n%d\n" % (self.k, self.bits, self.start, self.end, self.seed)
+        return head + self.level(self.levels - 1).tobytes()
+
+    def profile(self, on: bool = True) -> None:
+        self._lib.abg_kn_profile(self._h, int(on))
+
+    def profile_get(self, name: str) -> Tuple[float, int]:
+        ms, n = C.c_double(), C.c_uint64()
+        self._lib.abg_kn_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
+        return ms.value, n.value

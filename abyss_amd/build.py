@@ -54,6 +54,7 @@ OBJ_DIR = os.path.join(ROOT, "abyss_amd", "lib", "obj")
 UNITS = {
     "abg_kernels": ["abg_kernels.hip", "abg_core.h", "abg_engine.h", "abg_walk.h", "abg_host.h", "abg_overlap.h"],
     "abg_rr": ["abg_rr.hip", "abg_rr.h", "abg_core.h"],
+    "abg_kn": ["abg_kn.hip", "abg_kn.h", "abg_core.h"],
 }
 
 
@@ -115,6 +116,7 @@ def build_oracle(force: bool = False) -> None:
 READER_CHECK = os.path.join(ROOT, "tests", "hostcheck", "reader_check")
 ADJLIST_CHECK = os.path.join(ROOT, "tests", "hostcheck", "adjlist_check")
 RRESOLVER_CHECK = os.path.join(ROOT, "tests", "hostcheck", "rresolver_check")
+KN_CHECK = os.path.join(ROOT, "tests", "hostcheck", "kn_check")
 
 
 def build_hostcheck(force: bool = False) -> str:
@@ -133,6 +135,11 @@ def build_hostcheck(force: bool = False) -> str:
     csrc = os.path.join(ROOT, "tests", "hostcheck", "rresolver_check.cc")
     if force or _newer(RRESOLVER_CHECK, [csrc, os.path.join(CSRC, "abg_rr.h"), os.path.join(CSRC, "abg_core.h")] + hsrc):
         _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", RRESOLVER_CHECK, csrc, "-lpthread"])
+    ksrc = os.path.join(ROOT, "tests", "hostcheck", "kn_check.cc")
+    kdeps = [ksrc] + [os.path.join(CSRC, f) for f in ("abg_kn.h", "abg_core.h")] + \
+        [os.path.join(CSRC, "host", f) for f in ("bloom_core.h", "fasta_reader.h")]
+    if force or _newer(KN_CHECK, kdeps):
+        _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", KN_CHECK, ksrc, "-lpthread"])
     return HOSTCHECK
 
 

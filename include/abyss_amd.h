@@ -398,6 +398,41 @@ int abg_rr_sync(abg_rr* f);                           /* waits for everything qu
 int abg_rr_profile(abg_rr* f, int on);
 int abg_rr_profile_get(abg_rr* f, const char* name, double* total_ms, uint64_t* launches);
 
+
+/* ---- Konnector Bloom filters: `abyss-bloom build -t konnector` and the probes of `abyss-bloom kmers` (Bloom/bloom.cc) --------
+ * One hash per k-mer: index = CityHash64WithSeed(canonical k-mer packed 2 bits a base, (k + 3) / 4 bytes, seed) % full_bits
+ * (Bloom/Bloom.h Bloom::hash, Common/Kmer.cpp, Common/city.cc); bit i of a level is byte i / 8, bit 7 - i % 8
+ * (Bloom/BloomFilter.h).  A filter holds `levels` levels of the window [start, end] of the index space (end - start + 1 bits each,
+ * Bloom/BloomFilterWindow.h; start 0, end full_bits - 1 for a plain filter); an insert sets the first level whose bit is clear
+ * (Bloom/CascadingBloomFilter.h insert).  Sequences are ASCII with n + 1 offsets as in abg_load_seqs; every window of k characters
+ * that are all ACGT (either case) counts (Bloom.h loadSeq).  An abg_kn owns a HIP stream, the levels in device memory and its
+ * staging buffers; one abg_kn is not thread-safe. */
+typedef struct abg_kn abg_kn;
+/* CascadingBloomFilterWindow(full_bits, start, end, levels, seed) with Kmer::setLength(k), k 1..192 */
+int abg_kn_create(int device, uint64_t full_bits, uint32_t levels, uint32_t k, uint64_t seed, uint64_t start, uint64_t end,
+    abg_kn** out);
+void abg_kn_destroy(abg_kn* f);
+const char* abg_kn_last_error(const abg_kn* f); /* f may be NULL: the last failed abg_kn_create */
+/* one level's ceil((end - start + 1) / 8) bytes in (BloomFilter::read into a level, bloom.cc initBloomFilterLevels -L) and out
+ * (BloomFilter::write of the last level, CascadingBloomFilter::write) */
+int abg_kn_import(abg_kn* f, uint32_t level, const uint8_t* bytes);
+int abg_kn_export(abg_kn* f, uint32_t level, uint8_t* bytes);
+/* Bloom::loadSeq(filter, k, seq) for every sequence.  Returns once the caller's buffers have been read; the kernels may still be
+ * running (every other call orders itself behind them). */
+int abg_kn_insert_seqs(abg_kn* f, const char* seqs, const uint64_t* offsets, uint64_t n);
+/* bloom.cc memberOf: print[offsets[i] - offsets[0] + j] = 1 where window j of sequence i is all ACGT and its bit in level 0
+ * differs from `inverse` (-r), else 0; offsets[n] - offsets[0] bytes */
+int abg_kn_contains_seqs(abg_kn* f, const char* seqs, const uint64_t* offsets, uint64_t n, int inverse, uint8_t* print);
+/* BloomFilter::popcount() of every level: per_level[0 .. levels) */
+int abg_kn_popcount(abg_kn* f, uint64_t* per_level);
+/* Bloom::hash(Kmer(window j), seed) and its index % full_bits for every window j of seq (len - k + 1 of them), valid[j] = all
+ * ACGT (hash and index 0 where not); known-answer tests */
+int abg_kn_hash_seq(abg_kn* f, const char* seq, uint64_t len, uint64_t* hash, uint64_t* index, uint8_t* valid);
+int abg_kn_sync(abg_kn* f); /* waits for everything queued */
+/* kernel timing as abg_profile_enable / abg_profile_get: "kn_pack", "kn_insert", "kn_contains", "kn_popcount", "kn_hash" */
+int abg_kn_profile(abg_kn* f, int on);
+int abg_kn_profile_get(abg_kn* f, const char* name, double* total_ms, uint64_t* launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,40 @@
+"""The Konnector goldens (tests/golden/konnector, written by tests/golden/make_konnector.py): cases.json, and the reads, hash
+vectors and filter files packed in data.tar.gz."""
+import functools
+import io
+import json
+import os
+import tarfile
+
+from util import GOLDEN
+
+KN = os.path.join(GOLDEN, "konnector")
+
+
+@functools.lru_cache(maxsize=None)
+def cases():
+    return json.load(open(os.path.join(KN, "cases.json")))
+
+
+@functools.lru_cache(maxsize=None)
+def files():
+    """name -> bytes of every file in data.tar.gz"""
+    with tarfile.open(os.path.join(KN, "data.tar.gz"), "r:gz") as tar:
+        return {m.name: tar.extractfile(m).read() for m in tar.getmembers() if m.isfile()}
+
+
+def golden(name):
+    return files()[name]
+
+
+def hash_vectors():
+    return json.loads(golden("hash_vectors.json"))
+
+
+def workdir(tmp_path):
+    """The reads and every golden filter file written into tmp_path (commands refer to them by their plain names)."""
+    for name, data in files().items():
+        if name.endswith(".bloom") or name.startswith("reads."):
+            with open(os.path.join(str(tmp_path), name), "wb") as f:
+                f.write(data)
+    return str(tmp_path)
