@@ -1,6 +1,7 @@
 // abg_kn.hip -- gfx950 kernels and C ABI of the Konnector Bloom filter (include/abyss_amd.h, abg_kn_*; logic in abg_kn.h).
 //
-// A chunk of reads is staged as ASCII, one 'N' after every read (so no window spans two reads) and KN_PAD 'N's at the end.
+// A chunk of reads is staged as ASCII, one 'N' after every read (so no window spans two reads) and KN_PAD 'N's at the end.  A
+// read longer than a staging slot goes as pieces that overlap by k - 1 characters (each window in exactly one piece).
 //   k_kn_pack      one lane per 32 characters: two 16-byte loads, one 64-bit word of 2-bit codes and one 32-bit non-ACGT mask.
 //                  Streaming: 1.375 bytes of HBM traffic per base.
 //   k_kn_insert    one k-mer window per lane: the window's validity from the mask (at most 7 dwords, shared by neighbouring
@@ -20,6 +21,7 @@
 
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
@@ -121,6 +123,12 @@ __global__ void __launch_bounds__(256) k_kn_hash(abg::KnParams p, const uint64_t
 
 struct Prof { double ms = 0; uint64_t launches = 0; };
 
+// A piece of the caller's sequences: `len` characters from seqs + at.  A sequence that does not fit a slot is cut into pieces
+// that overlap by k - 1 characters, so that each of its windows lies in exactly one piece: a piece owns the windows that start
+// at its first `own` positions (all of them for the last piece of a sequence, len - k + 1 for the others, whose last k - 1
+// positions start the next piece).
+struct Piece { uint64_t at, len, own; };
+
 } // namespace
 
 struct abg_kn {
@@ -129,14 +137,16 @@ struct abg_kn {
 	abg::KnParams p;
 	uint64_t level_bits = 0, level_bytes = 0;
 	uint32_t* levels = nullptr; // p.levels levels, p.level_words 32-bit words apart
-	// two staging slots (pinned host memory the reads are packed into, device memory they are copied to, the event that says the
-	// slot's kernels are done with both); the codes and the mask are shared: the kernels of one stream run one after the other
-	static constexpr size_t SLOT = 64u << 20;
+	// two staging slots of `slot` bytes (pinned host memory the reads are packed into, device memory they are copied to, the event
+	// that says the slot's kernels are done with both); the codes and the mask are shared: the kernels of one stream run one after
+	// the other.  64 MiB; ABG_KN_SLOT_BYTES overrides it (tests: many slots and sequences cut into many pieces)
+	size_t slot = 64u << 20;
 	char* pin[2] = { nullptr, nullptr };
 	char* dev[2] = { nullptr, nullptr };
 	hipEvent_t done[2] = { nullptr, nullptr };
 	bool busy[2] = { false, false };
 	int next = 0;
+	std::vector<Piece> staged; // the pieces of the chunk last staged, in order
 	uint64_t* codes = nullptr;
 	uint32_t* bad = nullptr;
 	unsigned long long* aux = nullptr; size_t aux_cap = 0; // print flags / hash outputs
@@ -204,19 +214,43 @@ void prof_drain(abg_kn* f)
 	f->pending.clear();
 }
 
-// staged bytes of reads [a, b): each read and one 'N'
-uint64_t staged_bytes(const uint64_t* off, uint64_t a, uint64_t b) { return off[b] - off[a] + (b - a); }
+// Staged bytes that fit a slot: each piece and its 'N', then padding up to a multiple of 32 plus KN_PAD (slot is a multiple of 32)
+uint64_t slot_room(const abg_kn* f) { return f->slot - abg::KN_PAD - 32; }
 
-// the reads [a, b) into dst as staged: read, 'N', read, 'N', ..., then 'N' up to a multiple of 32 plus KN_PAD; returns the
-// staged length before the padding
-uint64_t stage(char* dst, const char* seqs, const uint64_t* off, uint64_t a, uint64_t b)
+// the next piece from the cursor (sequence i, character s of it) on; moves the cursor past what the piece owns
+Piece next_piece(const uint64_t* off, uint64_t& i, uint64_t& s, uint64_t cap, uint32_t k)
 {
+	const uint64_t left = off[i + 1] - off[i] - s;
+	Piece p{ off[i] + s, left, left };
+	if (left > cap) {
+		p.len = cap;
+		p.own = cap - (k - 1);
+		s += p.own;
+	} else {
+		i++;
+		s = 0;
+	}
+	return p;
+}
+
+// pieces from the cursor on into dst as staged: piece, 'N', piece, 'N', ..., then 'N' up to a multiple of 32 plus KN_PAD, as
+// many as fit a slot (at least one: no piece is longer than the room less its 'N'); f->staged lists them; returns the staged
+// length before the padding
+uint64_t stage(abg_kn* f, char* dst, const char* seqs, const uint64_t* off, uint64_t n, uint64_t& i, uint64_t& s)
+{
+	const uint64_t room = slot_room(f);
+	f->staged.clear();
 	uint64_t at = 0;
-	for (uint64_t i = a; i < b; i++) {
-		const uint64_t len = off[i + 1] - off[i];
-		memcpy(dst + at, seqs + off[i], len);
-		dst[at + len] = 'N';
-		at += len + 1;
+	while (i < n) {
+		uint64_t ni = i, ns = s;
+		const Piece p = next_piece(off, ni, ns, room - 1, f->p.k);
+		if (at + p.len + 1 > room) break;
+		memcpy(dst + at, seqs + p.at, p.len);
+		dst[at + p.len] = 'N';
+		at += p.len + 1;
+		f->staged.push_back(p);
+		i = ni;
+		s = ns;
 	}
 	const uint64_t end = (at + 31) / 32 * 32 + abg::KN_PAD;
 	memset(dst + at, 'N', end - at);
@@ -269,35 +303,16 @@ int wait_slot(abg_kn* f, int s)
 	return ABG_OK;
 }
 
-// the reads [a, b) staged into slot s, copied to the device and packed; *len: the staged length
-int upload(abg_kn* f, int s, const char* seqs, const uint64_t* off, uint64_t a, uint64_t b, uint64_t* len)
+// the pieces from the cursor on that fit slot s, staged into it, copied to the device and packed; *len: the staged length
+int upload(abg_kn* f, int s, const char* seqs, const uint64_t* off, uint64_t n, uint64_t& i, uint64_t& c, uint64_t* len)
 {
 	int rc = wait_slot(f, s);
 	if (rc != ABG_OK) return rc;
-	*len = stage(f->pin[s], seqs, off, a, b);
+	*len = stage(f, f->pin[s], seqs, off, n, i, c);
 	const uint64_t padded = (*len + 31) / 32 * 32 + abg::KN_PAD;
 	hipError_t e = hipMemcpyAsync(f->dev[s], f->pin[s], padded, hipMemcpyHostToDevice, f->stream);
 	if (!kn_ok(f, e, "copying reads to the device")) return kn_code_of(e);
 	return launch_pack(f, f->dev[s], *len);
-}
-
-// reads [a, b) that fit one slot, from a on (at least one read; a read longer than a slot is refused by the caller)
-uint64_t slot_end(const uint64_t* off, uint64_t a, uint64_t n)
-{
-	const uint64_t cap = abg_kn::SLOT - abg::KN_PAD - 32;
-	uint64_t lo = a + 1, hi = n; // the largest b in [a + 1, n] with staged_bytes(a, b) <= cap
-	while (lo < hi) {
-		const uint64_t mid = lo + (hi - lo + 1) / 2;
-		if (staged_bytes(off, a, mid) <= cap) lo = mid; else hi = mid - 1;
-	}
-	return lo;
-}
-
-int check_lengths(abg_kn* f, const uint64_t* off, uint64_t n)
-{
-	for (uint64_t i = 0; i < n; i++)
-		if (off[i + 1] - off[i] + 1 > abg_kn::SLOT - abg::KN_PAD - 32) { f->error = "a sequence longer than a staging slot (64 MB)"; return ABG_EINVAL; }
-	return ABG_OK;
 }
 
 } // namespace
@@ -320,11 +335,12 @@ int abg_kn_create(int device, uint64_t full_bits, uint32_t levels, uint32_t k, u
 	f->p = abg::make_kn_params(k, seed, full_bits, levels, start, end);
 	f->level_bits = end - start + 1;
 	f->level_bytes = (f->level_bits + 7) / 8;
+	if (const char* v = getenv("ABG_KN_SLOT_BYTES")) f->slot = std::max<size_t>(1024, strtoull(v, nullptr, 10)) / 32 * 32; // (tests)
 	hipError_t e = hipSetDevice(device);
 	hipDeviceProp_t prop;
 	if (e == hipSuccess && hipGetDeviceProperties(&prop, device) == hipSuccess) f->cus = (uint32_t)prop.multiProcessorCount;
 	const size_t lbytes = (size_t)f->p.level_words * 4 * levels;
-	const size_t words = abg_kn::SLOT / 32 + 16;
+	const size_t words = f->slot / 32 + 16;
 	if (e == hipSuccess) e = hipStreamCreate(&f->stream);
 	if (e == hipSuccess) e = hipMalloc((void**)&f->levels, lbytes);
 	if (e == hipSuccess) e = hipMemsetAsync(f->levels, 0, lbytes, f->stream);
@@ -332,8 +348,8 @@ int abg_kn_create(int device, uint64_t full_bits, uint32_t levels, uint32_t k, u
 	if (e == hipSuccess) e = hipMalloc((void**)&f->bad, words * 4);
 	if (e == hipSuccess) e = hipMalloc((void**)&f->d_count, 8);
 	for (int i = 0; i < 2 && e == hipSuccess; i++) {
-		e = hipHostMalloc((void**)&f->pin[i], abg_kn::SLOT, hipHostMallocDefault);
-		if (e == hipSuccess) e = hipMalloc((void**)&f->dev[i], abg_kn::SLOT);
+		e = hipHostMalloc((void**)&f->pin[i], f->slot, hipHostMallocDefault);
+		if (e == hipSuccess) e = hipMalloc((void**)&f->dev[i], f->slot);
 		if (e == hipSuccess) e = hipEventCreateWithFlags(&f->done[i], hipEventDisableTiming);
 	}
 	if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
@@ -374,20 +390,18 @@ int abg_kn_insert_seqs(abg_kn* f, const char* seqs, const uint64_t* offsets, uin
 	if (!f || (n && (!seqs || !offsets))) return ABG_EINVAL;
 	if (n == 0) return ABG_OK;
 	(void)hipSetDevice(f->device);
-	int rc = check_lengths(f, offsets, n);
-	for (uint64_t a = 0; rc == ABG_OK && a < n;) {
-		const uint64_t b = slot_end(offsets, a, n);
+	int rc = ABG_OK;
+	for (uint64_t i = 0, c = 0; rc == ABG_OK && i < n;) {
 		const int s = f->next;
 		f->next ^= 1;
 		uint64_t len = 0;
-		rc = upload(f, s, seqs, offsets, a, b, &len);
+		rc = upload(f, s, seqs, offsets, n, i, c, &len);
 		if (rc == ABG_OK) rc = launch_insert(f, len);
 		if (rc == ABG_OK) {
 			const hipError_t e = hipEventRecord(f->done[s], f->stream);
 			if (!kn_ok(f, e, "hipEventRecord")) rc = kn_code_of(e);
 			else f->busy[s] = true;
 		}
-		a = b;
 	}
 	return rc;
 }
@@ -397,15 +411,14 @@ int abg_kn_contains_seqs(abg_kn* f, const char* seqs, const uint64_t* offsets, u
 	if (!f || (n && (!seqs || !offsets || !print))) return ABG_EINVAL;
 	if (n == 0) return ABG_OK;
 	(void)hipSetDevice(f->device);
-	int rc = check_lengths(f, offsets, n);
-	if (rc == ABG_OK && !grow_aux(f, (abg_kn::SLOT / 64 + 1) * 8)) rc = ABG_ENOMEM;
+	int rc = ABG_OK;
+	if (!grow_aux(f, (f->slot / 64 + 1) * 8)) rc = ABG_ENOMEM;
 	std::vector<unsigned long long> bits;
-	for (uint64_t a = 0; rc == ABG_OK && a < n;) {
-		const uint64_t b = slot_end(offsets, a, n);
+	for (uint64_t i = 0, c = 0; rc == ABG_OK && i < n;) {
 		const int s = f->next;
 		f->next ^= 1;
 		uint64_t len = 0;
-		rc = upload(f, s, seqs, offsets, a, b, &len);
+		rc = upload(f, s, seqs, offsets, n, i, c, &len);
 		if (rc != ABG_OK) break;
 		{
 			Timed t(f, "kn_contains");
@@ -420,15 +433,14 @@ int abg_kn_contains_seqs(abg_kn* f, const char* seqs, const uint64_t* offsets, u
 		hipError_t e = hipMemcpyAsync(bits.data(), f->aux, bits.size() * 8, hipMemcpyDeviceToHost, f->stream);
 		if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
 		if (!kn_ok(f, e, "reading the probes back")) { rc = kn_code_of(e); break; }
-		// staged position -> the caller's position (read i of the chunk starts i characters later than in the caller's buffer)
+		// staged position -> the caller's position: each piece's flags go to where it came from, up to the positions it owns
+		// (the next piece writes the rest)
 		uint64_t at = 0;
-		for (uint64_t i = a; i < b; i++) {
-			const uint64_t len_i = offsets[i + 1] - offsets[i];
-			uint8_t* dst = print + (offsets[i] - offsets[0]);
-			for (uint64_t j = 0; j < len_i; j++, at++) dst[j] = (uint8_t)((bits[at >> 6] >> (at & 63)) & 1);
-			at++;
+		for (const Piece& pc : f->staged) {
+			uint8_t* dst = print + (pc.at - offsets[0]);
+			for (uint64_t j = 0; j < pc.own; j++) dst[j] = (uint8_t)((bits[(at + j) >> 6] >> ((at + j) & 63)) & 1);
+			at += pc.len + 1;
 		}
-		a = b;
 	}
 	return rc;
 }
@@ -458,16 +470,15 @@ int abg_kn_hash_seq(abg_kn* f, const char* seq, uint64_t len, uint64_t* hash, ui
 {
 	if (!f || (len && (!seq || !hash || !index || !valid))) return ABG_EINVAL;
 	if (len < f->p.k) return ABG_OK;
+	if (len + 1 > slot_room(f)) { f->error = "abg_kn_hash_seq takes a sequence that fits one staging slot"; return ABG_EINVAL; }
 	const uint64_t off[2] = { 0, len };
-	int rc = check_lengths(f, off, 1);
-	if (rc != ABG_OK) return rc;
 	(void)hipSetDevice(f->device);
 	const uint64_t npos = len - f->p.k + 1;
 	if (!grow_aux(f, npos * 17 + 16)) return ABG_ENOMEM;
 	const int s = f->next;
 	f->next ^= 1;
-	uint64_t staged = 0;
-	rc = upload(f, s, seq, off, 0, 1, &staged);
+	uint64_t staged = 0, i = 0, c = 0;
+	int rc = upload(f, s, seq, off, 1, i, c, &staged);
 	if (rc != ABG_OK) return rc;
 	unsigned long long* dh = f->aux;
 	unsigned long long* di = f->aux + npos;

@@ -417,16 +417,18 @@ const char* abg_kn_last_error(const abg_kn* f); /* f may be NULL: the last faile
  * (BloomFilter::write of the last level, CascadingBloomFilter::write) */
 int abg_kn_import(abg_kn* f, uint32_t level, const uint8_t* bytes);
 int abg_kn_export(abg_kn* f, uint32_t level, uint8_t* bytes);
-/* Bloom::loadSeq(filter, k, seq) for every sequence.  Returns once the caller's buffers have been read; the kernels may still be
- * running (every other call orders itself behind them). */
+/* Bloom::loadSeq(filter, k, seq) for every sequence, of any length (one longer than a staging slot, 64 MiB, goes through it as
+ * pieces that overlap by k - 1 bases: every window is inserted once).  Returns once the caller's buffers have been read; the
+ * kernels may still be running (every other call orders itself behind them). */
 int abg_kn_insert_seqs(abg_kn* f, const char* seqs, const uint64_t* offsets, uint64_t n);
 /* bloom.cc memberOf: print[offsets[i] - offsets[0] + j] = 1 where window j of sequence i is all ACGT and its bit in level 0
- * differs from `inverse` (-r), else 0; offsets[n] - offsets[0] bytes */
+ * differs from `inverse` (-r), else 0; offsets[n] - offsets[0] bytes; sequences of any length, as abg_kn_insert_seqs */
 int abg_kn_contains_seqs(abg_kn* f, const char* seqs, const uint64_t* offsets, uint64_t n, int inverse, uint8_t* print);
 /* BloomFilter::popcount() of every level: per_level[0 .. levels) */
 int abg_kn_popcount(abg_kn* f, uint64_t* per_level);
 /* Bloom::hash(Kmer(window j), seed) and its index % full_bits for every window j of seq (len - k + 1 of them), valid[j] = all
- * ACGT (hash and index 0 where not); known-answer tests */
+ * ACGT (hash and index 0 where not); known-answer tests, so seq must fit one staging slot (len < 64 MiB - 288; ABG_EINVAL
+ * otherwise) */
 int abg_kn_hash_seq(abg_kn* f, const char* seq, uint64_t len, uint64_t* hash, uint64_t* index, uint8_t* valid);
 int abg_kn_sync(abg_kn* f); /* waits for everything queued */
 /* kernel timing as abg_profile_enable / abg_profile_get: "kn_pack", "kn_insert", "kn_contains", "kn_popcount", "kn_hash" */

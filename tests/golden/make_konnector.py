@@ -6,7 +6,8 @@ It compiles Bloom/bloom.cc with the nine Common/DataLayer sources of oracle/Make
 property-map header that bloom.cc reaches through the shim) into a temporary directory, and a small known-answer driver that
 links Common/Kmer.cpp and Common/city.cc and prints Bloom::hash(Kmer(window), seed) for every window.  Nothing under oracle/ is
 changed.  Run in the build container (needs the reference sources):
-    python tests/golden/make_konnector.py
+    python tests/golden/make_konnector.py [--no-large]
+The large cases (large.json: filters past 2^32 bits, records longer than a staging slot) take a few minutes.
 """
 import hashlib
 import json
@@ -164,6 +165,16 @@ BUILDS = [
     ("k96_l2", ["-k96", "-b64K", "-l2", "reads.fa"]),
     ("k150_l1", ["-k150", "-b32K", "reads.fa", "reads.fq"]),
     ("k33_l3_w2", ["-k33", "-b96K", "-l3", "-w", "2/2", "reads.fa"]),
+    # every width of the insert kernel (NW = ceil(k / 32)) and its edges in a cascade; odd -b: bits a level neither a power of
+    # two nor a multiple of 8
+    ("k12_l2", ["-k12", "-b32K", "-l2", "reads.fa"]),
+    ("k31_l3_odd", ["-k31", "-b24001", "-l3", "reads.fa"]),  # 64002 bits a level
+    ("k32_l2", ["-k32", "-b32K", "-l2", "reads.fa", "reads.fq"]),
+    ("k97_l2_odd", ["-k97", "-b24577", "-l2", "reads.fa"]),  # 98308 bits a level
+    ("k128_l3", ["-k128", "-b48K", "-l3", "reads.fa", "reads.fq"]),
+    ("k160_l2", ["-k160", "-b32K", "-l2", "reads.fa"]),
+    ("k161_l3_odd", ["-k161", "-b30001", "-l3", "reads.fa"]),  # 80002 bits a level
+    ("k192_l2", ["-k192", "-b64K", "-l2", "reads.fa"]),
 ]
 
 # name, argv after the program (files refer to the builds above); outputs named out_<name>.bloom are kept
@@ -196,6 +207,23 @@ KMERS = [
     ("kmers_raw_r", ["kmers", "-k25", "--raw", "-r", "k25_l2.bloom", "reads.fa"]),
     ("kmers_k64_window", ["kmers", "-k64", "--bed", "k64_l1_hbig.bloom", "reads.fq"]),
     ("kmers_k150", ["kmers", "-k150", "k150_l1.bloom", "reads.fa"]),
+    ("kmers_k128_bed", ["kmers", "-k128", "--bed", "k128_l3.bloom", "reads.fa"]),
+    ("kmers_k128_raw_r", ["kmers", "-k128", "--raw", "-r", "k128_l3.bloom", "reads.fa"]),
+    ("kmers_k192_bed_r", ["kmers", "-k192", "--bed", "-r", "k192_l2.bloom", "reads.fa"]),
+    ("kmers_k192_raw", ["kmers", "-k192", "--raw", "k192_l2.bloom", "reads.fa"]),
+]
+
+# large.json: name, the cases that must run first (their outputs are inputs), argv; outputs are kept as sha256 and byte count.
+# reads.fa and reads.fq are the archive's; long.fa comes from tests/kn_large.py
+LARGE = [
+    ("build_b2G_l3", [], ["build", "-k64", "-b2G", "-l3", "l3.bloom", "reads.fa"]),  # 5,726,623,061 bits a level: odd, > 2^32
+    ("build_b2G_l2", [], ["build", "-k64", "-b2G", "-l2", "l2.bloom", "reads.fa"]),  # 2^33 bits a level
+    ("build_b1G_w4", [], ["build", "-k64", "-b1G", "-w", "4/4", "w4.bloom", "reads.fq"]),  # the window starts at bit 6,442,450,944
+    ("kmers_b2G_l3_bed", ["build_b2G_l3"], ["kmers", "-k64", "--bed", "l3.bloom", "reads.fa"]),
+    ("info_b2G_l3", ["build_b2G_l3"], ["info", "-k64", "l3.bloom"]),
+    ("build_long_b64M_l2", [], ["build", "-k64", "-b64M", "-l2", "long.bloom", "long.fa"]),
+    ("build_reads_b64M", [], ["build", "-k64", "-b64M", "reads64M.bloom", "reads.fa"]),
+    ("kmers_long_bed", ["build_reads_b64M"], ["kmers", "-k64", "--bed", "reads64M.bloom", "long.fa"]),
 ]
 
 
@@ -229,6 +257,47 @@ def write_cases(cases):
             f.write(",\n".join("  " + json.dumps(r) for r in cases[kind]))
             f.write("\n ]%s\n" % ("," if i < 2 else ""))
         f.write("}\n")
+
+
+def digest(data):
+    """stdout or stderr as text when short, else as sha256, byte count and line count"""
+    if len(data) <= 4096:
+        return {"text": data.decode()}
+    return {"sha256": hashlib.sha256(data).hexdigest(), "bytes": len(data), "lines": data.count(b"\n")}
+
+
+def large_cases(exe, files, tmp):
+    """large.json: every LARGE case run by the reference, its outputs kept as digests (and deleted once digested)."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import kn_large
+    work = os.path.join(tmp, "large")
+    os.makedirs(work)
+    inputs = {}
+    for name in ("reads.fa", "reads.fq"):
+        open(os.path.join(work, name), "wb").write(files[name])
+        inputs[name] = {"sha256": hashlib.sha256(files[name]).hexdigest(), "bytes": len(files[name])}
+    sha, size = kn_large.write_long_fasta(os.path.join(work, "long.fa"), files["reads.fa"])
+    inputs["long.fa"] = {"sha256": sha, "bytes": size}
+    out = []
+    for name, needs, argv in LARGE:
+        before = set(os.listdir(work))
+        st, so, se = run(exe, argv, work)
+        assert st == 0, (name, se)
+        outputs = {}
+        for f in sorted(set(os.listdir(work)) - before):
+            sha, size = kn_large.sha256_file(os.path.join(work, f))
+            outputs[f] = {"sha256": sha, "bytes": size}
+        out.append({"name": name, "needs": needs, "argv": argv, "status": st, "stdout": digest(so), "stderr": digest(se),
+                    "outputs": outputs})
+        for c in out:  # outputs no later case needs go
+            if not any(c["name"] in n for _, n, _ in LARGE[len(out):]):
+                for f in c["outputs"]:
+                    if os.path.exists(os.path.join(work, f)):
+                        os.remove(os.path.join(work, f))
+    with open(os.path.join(OUT, "large.json"), "w") as f:
+        f.write('{\n "inputs": %s,\n "cases": [\n' % json.dumps(inputs))
+        f.write(",\n".join("  " + json.dumps(c) for c in out))
+        f.write("\n ]\n}\n")
 
 
 def main():
@@ -265,6 +334,8 @@ def main():
             assert st == 0, (name, err)
             cases["kmers"].append({"name": name, "argv": argv, "status": st, "sha256": hashlib.sha256(out).hexdigest(),
                                    "lines": out.count(b"\n")})
+        if "--no-large" not in sys.argv:
+            large_cases(exe, files, tmp)
     write_data(files)
     write_cases(cases)
     print("wrote", OUT)

@@ -38,3 +38,16 @@ def workdir(tmp_path):
             with open(os.path.join(str(tmp_path), name), "wb") as f:
                 f.write(data)
     return str(tmp_path)
+
+
+@functools.lru_cache(maxsize=None)
+def large():
+    """large.json: the digests of the large cases (filters past 2^32 bits, records longer than a staging slot)."""
+    return json.load(open(os.path.join(KN, "large.json")))
+
+
+def filter_header(data):
+    """(k, bits, start, end, seed) and the level's bytes of a filter file (Bloom::writeHeader: version, k, size and window, seed)."""
+    lines = data.split(b"\n", 4)
+    bits, start, end = (int(x) for x in lines[2].split(b"\t"))
+    return (int(lines[1]), bits, start, end, int(lines[3])), lines[4]

@@ -1,15 +1,18 @@
 """Konnector Bloom filters on the GPU (abg_kn.hip through api.KonnectorBloom and abyss_amd/bin/abyss-bloom) against the
-reference's own outputs (tests/golden/konnector, made by tests/golden/make_konnector.py) and the host restatement
-(tests/hostcheck/kn_check)."""
+reference's own outputs (tests/golden/konnector, made by tests/golden/make_konnector.py: cases.json and, for filters past 2^32
+bits and records longer than a staging slot, large.json), the host restatement (tests/hostcheck/kn_check) and plain Python
+restatements of the index and the cascade."""
 import hashlib
 import os
+import re
 import subprocess
 
 import numpy as np
 import pytest
 
 from abyss_amd import api, build, synth
-from kn_golden import cases, golden, hash_vectors, workdir
+import kn_large
+from kn_golden import cases, filter_header, golden, hash_vectors, large, workdir
 
 pytestmark = pytest.mark.gpu
 
@@ -24,8 +27,9 @@ def kn_check():
     return build.KN_CHECK
 
 
-def run(argv, cwd, timeout=300):
-    return subprocess.run([abyss_bloom()] + argv, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
+def run(argv, cwd, timeout=300, env=None):
+    return subprocess.run([abyss_bloom()] + argv, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout,
+                          env=None if env is None else dict(os.environ, **env))
 
 
 def test_hash_seq_known_answers():
@@ -135,3 +139,217 @@ def test_api_cascade_and_popcount():
         assert flags.sum() > 0
     finally:
         f.close()
+
+
+# ---- the index space: mod64 on the device for every kind of filter size ---------------------------------------------------
+
+MOD_BITS = [3, 64, 1000003, (1 << 32) - 1, 1 << 32, (1 << 32) + 15, 5726623061, 1 << 33, 38177487104, 1 << 40, (1 << 63) + 12345,
+            (1 << 64) - 59]
+
+
+def test_hash_seq_index_for_every_filter_size(monkeypatch):
+    """index = hash % bits on the device (abg::mod64: a mask for powers of two, a multiply-high otherwise) for sizes past 2^32
+    and up to 2^64 - 59, against Python's integers.  A window of at most 4096 bits keeps each filter tiny."""
+    monkeypatch.setenv("ABG_KN_SLOT_BYTES", "65536")
+    by_key = {}
+    for v in hash_vectors():
+        by_key.setdefault((v["k"], int(v["seed"])), []).append(v)
+    for bits in MOD_BITS:
+        for (k, seed), vs in sorted(by_key.items()):
+            f = api.KonnectorBloom(k, bits, seed=seed, start=0, end=min(bits - 1, 4095))
+            try:
+                for v in vs:
+                    h, i, ok = f.hash_seq(v["seq"].encode())
+                    want = [int(w) for w in v["hash"] if w is not None]
+                    assert [int(x) for x in h[ok]] == want, (bits, k, seed)
+                    assert [int(x) for x in i[ok]] == [w % bits for w in want], (bits, k, seed)
+            finally:
+                f.close()
+
+
+# ---- bit placement at high offsets: a window past 2^32 of a 5,726,623,061-bit cascade --------------------------------------
+
+def restated_levels(hashes, bits, start, end, levels):
+    """CascadingBloomFilterWindow::insert, restated: index = hash % bits; inside [start, end] local bit i sets byte i // 8,
+    bit 7 - i % 8 of the first level where it is clear.  Returns {byte: value} for each level."""
+    have = [set() for _ in range(levels)]
+    for h in hashes:
+        idx = h % bits
+        if start <= idx <= end:
+            for lv in have:
+                if idx - start not in lv:
+                    lv.add(idx - start)
+                    break
+    out = []
+    for lv in have:
+        d = {}
+        for i in lv:
+            d[i // 8] = d.get(i // 8, 0) | (1 << (7 - i % 8))
+        out.append(d)
+    return out
+
+
+@pytest.mark.parametrize("k,seed_i", [(5, 0), (33, 1), (96, 2), (128, 0), (150, 1), (192, 2)])
+def test_bit_placement_past_2_32(k, seed_i):
+    bits, levels = 5726623061, 3
+    start, end = bits - (1 << 31), bits - 1
+    vec = hash_vectors()
+    seed = int(sorted({v["seed"] for v in vec}, key=int)[seed_i])
+    vs = [v for v in vec if v["k"] == k and int(v["seed"]) == seed]
+    assert len(vs) == 5
+    seqs = [v["seq"].encode() for v in vs] + [vs[0]["seq"].encode()]  # the first twice: its windows reach level 2
+    hashes = [int(w) for v in vs + [vs[0]] for w in v["hash"] if w is not None]
+    want = restated_levels(hashes, bits, start, end, levels)
+    assert want[0] and want[1] and sum(len(w) for w in want) > 0
+    b, off = api.concat_seqs(seqs)
+    f = api.KonnectorBloom(k, bits, levels=levels, seed=seed, start=start, end=end)
+    try:
+        f.load(b, off)
+        for lv in range(levels):
+            got = f.level(lv)
+            assert got.size == (1 << 28)
+            nz = np.flatnonzero(got)
+            assert [int(x) for x in nz] == sorted(want[lv]), lv
+            assert [int(got[x]) for x in nz] == [want[lv][x] for x in sorted(want[lv])], lv
+        assert f.popcount() == [sum(bin(x).count("1") for x in w.values()) for w in want]
+        flags = f.contains(b, off)
+        at = 0
+        for v in vs + [vs[0]]:  # level 0 holds exactly the in-window indices of the windows loaded
+            exp = [w is not None and start <= int(w) % bits <= end for w in v["hash"]]
+            assert [bool(x) for x in flags[at:at + len(exp)]] == exp
+            assert not flags[at + len(exp):at + len(v["seq"])].any()
+            at += len(v["seq"])
+    finally:
+        f.close()
+
+
+# ---- large cases: digests of the reference's outputs (tests/golden/konnector/large.json) -----------------------------------
+
+@pytest.fixture(scope="module")
+def large_dir(tmp_path_factory):
+    """reads.fa, reads.fq and long.fa (tests/kn_large.py), each checked against large.json's digest."""
+    d = str(tmp_path_factory.mktemp("kn_large"))
+    inputs = large()["inputs"]
+    for name in ("reads.fa", "reads.fq"):
+        open(os.path.join(d, name), "wb").write(golden(name))
+    kn_large.write_long_fasta(os.path.join(d, "long.fa"), golden("reads.fa"))
+    for name, want in inputs.items():
+        assert kn_large.sha256_file(os.path.join(d, name)) == (want["sha256"], want["bytes"]), name
+    return d
+
+
+def check_stream(got, want):
+    if "text" in want:
+        assert got.decode() == want["text"]
+    else:
+        assert (hashlib.sha256(got).hexdigest(), len(got), got.count(b"\n")) == (want["sha256"], want["bytes"], want["lines"])
+
+
+def large_params():
+    out = []
+    for c in large()["cases"]:
+        out.append(pytest.param(c["name"], None, id=c["name"]))
+        if any(a == "long.fa" for a in c["argv"]):  # the long records again through 64 KiB slots: ~2,300 pieces
+            out.append(pytest.param(c["name"], "65536", id=c["name"] + "-slot64K"))
+    return out
+
+
+@pytest.mark.parametrize("name,slot", large_params())
+def test_large_case_digests(large_dir, name, slot):
+    by_name = {c["name"]: c for c in large()["cases"]}
+    c = by_name[name]
+    env = {} if slot is None else {"ABG_KN_SLOT_BYTES": slot}
+    made = []
+    try:
+        for n in c["needs"]:
+            r = run(by_name[n]["argv"], large_dir, env=env)
+            assert r.returncode == 0, r.stderr
+            made += list(by_name[n]["outputs"])
+        made += list(c["outputs"])
+        r = run(c["argv"], large_dir, env=env)
+        assert r.returncode == c["status"], r.stderr
+        check_stream(r.stdout, c["stdout"])
+        check_stream(r.stderr, c["stderr"])
+        for out, want in c["outputs"].items():
+            got = kn_large.sha256_file(os.path.join(large_dir, out))
+            os.remove(os.path.join(large_dir, out))
+            assert got == (want["sha256"], want["bytes"]), out
+    finally:
+        for out in made:
+            if os.path.exists(os.path.join(large_dir, out)):
+                os.remove(os.path.join(large_dir, out))
+
+
+# ---- slot-size invariance: staging slots of 1, 4 and 64 KiB give the reference's bytes ---------------------------------------
+
+SLOTS = ["1024", "4096", "65536"]
+
+
+@pytest.mark.parametrize("slot", SLOTS)
+def test_small_slots_build_goldens(tmp_path, slot):
+    wd = workdir(tmp_path)
+    for c in cases()["build"]:
+        i = next(j for j, a in enumerate(c["args"]) if a.startswith("reads."))
+        out = "slot_%s.bloom" % c["name"]
+        r = run(["build"] + c["args"][:i] + [out] + c["args"][i:], wd, env={"ABG_KN_SLOT_BYTES": slot})
+        assert r.returncode == c["status"], (c["name"], r.stderr)
+        assert r.stderr.decode() == c["stderr"], c["name"]
+        assert open(os.path.join(wd, out), "rb").read() == golden(c["name"] + ".bloom"), c["name"]
+
+
+@pytest.mark.parametrize("slot", SLOTS)
+@pytest.mark.parametrize("name", ["kmers_bed", "kmers_k192_bed_r"])
+def test_small_slots_kmers_goldens(tmp_path, slot, name):
+    c = next(c for c in cases()["kmers"] if c["name"] == name)
+    r = run(c["argv"], workdir(tmp_path), env={"ABG_KN_SLOT_BYTES": slot})
+    assert r.returncode == c["status"], r.stderr
+    assert r.stdout.count(b"\n") == c["lines"]
+    assert hashlib.sha256(r.stdout).hexdigest() == c["sha256"]
+
+
+def joined_reads(per):
+    """reads.fa's records as the reader hands them over (masked, lower-case ends trimmed: FastaReader trimMasked) joined by
+    'N' into sequences of `per` records: the same windows as the records, in sequences longer than a small slot (so they are
+    cut into pieces)."""
+    recs = [re.sub(rb"^[a-z]+|[a-z]+$", b"", r) for r in kn_large.fasta_records(golden("reads.fa"))]
+    return api.concat_seqs([b"N".join(recs[i:i + per]) for i in range(0, len(recs), per)])
+
+
+# build goldens of reads.fa alone without -w, -L or -q: the API restates them from the joined records
+API_BUILDS = ["k25_l2", "k25_l3_odd", "k64_l1_hbig", "k96_l2", "k12_l2", "k31_l3_odd", "k97_l2_odd", "k160_l2", "k161_l3_odd",
+              "k192_l2"]
+
+
+@pytest.mark.parametrize("slot", SLOTS)
+def test_small_slots_api_load_and_contains(monkeypatch, slot):
+    monkeypatch.setenv("ABG_KN_SLOT_BYTES", slot)
+    b, off = joined_reads(1000)
+    assert int(np.diff(off).min()) > 100000
+    for name in API_BUILDS:
+        c = next(c for c in cases()["build"] if c["name"] == name)
+        (k, bits, start, end, seed), want = filter_header(golden(name + ".bloom"))
+        levels = next((int(a[2:]) for a in c["args"] if a.startswith("-l")), 1)
+        f = api.KonnectorBloom(k, bits, levels=levels, seed=seed, start=start, end=end)
+        try:
+            f.load(b, off)
+            assert f.level(levels - 1).tobytes() == want, name
+            assert f.popcount() == [int(x) for x in re.findall(r"Bloom popcount \(bits\): (\d+)", c["stderr"])], name
+        finally:
+            f.close()
+    # a filter of reads.fa holds every window of them: the flags are exactly the all-ACGT windows, in the caller's positions
+    for name in ("k25_l1", "k64_l1_hbig"):
+        (k, bits, start, end, seed), data = filter_header(golden(name + ".bloom"))
+        f = api.KonnectorBloom(k, bits, seed=seed, start=start, end=end)
+        try:
+            f.set_level(0, np.frombuffer(data, dtype=np.uint8))
+            flags = f.contains(b, off)
+            acgt = np.isin(np.frombuffer(b, dtype=np.uint8), np.frombuffer(b"ACGTacgt", dtype=np.uint8))
+            want = np.zeros(len(b), dtype=bool)
+            for s, e in zip(off[:-1].astype(np.int64), off[1:].astype(np.int64)):
+                full = np.convolve(acgt[s:e], np.ones(k, dtype=np.int64), mode="valid") == k
+                want[s:s + len(full)] = full
+            assert want.sum() > 100000
+            assert np.array_equal(flags.astype(bool), want), name
+            assert not f.contains(b, off, inverse=True).any(), name
+        finally:
+            f.close()

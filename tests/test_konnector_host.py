@@ -2,13 +2,15 @@
 CityHash64WithSeed) against known-answer vectors of the reference's own Kmer + city.cc, and the file commands of
 `abyss-bloom` (union, intersect, info, compare: host-side streaming that never starts the HIP runtime) against the
 reference's outputs (tests/golden/konnector, made by tests/golden/make_konnector.py)."""
+import hashlib
 import os
 import subprocess
 
 import pytest
 
 from abyss_amd import build
-from kn_golden import cases, golden, hash_vectors, workdir
+import kn_large
+from kn_golden import cases, golden, hash_vectors, large, workdir
 
 
 def abyss_bloom():
@@ -109,3 +111,21 @@ def test_host_restatement_builds_the_reference_files(tmp_path):
         subprocess.run([kn_check(), "build", str(k), str(seed), str(levels), str(bits), str(start), str(end), out] + reads,
                        cwd=wd, check=True)
         assert open(out, "rb").read() == golden(name + ".bloom"), name
+
+
+def test_large_inputs_regenerate(tmp_path):
+    """The large GPU cases regenerate long.fa (tests/kn_large.py) on the machine that runs them: its bytes must still be the ones
+    the reference ran on (large.json), and the archive's reads too."""
+    inputs = large()["inputs"]
+    assert set(inputs) == {"reads.fa", "reads.fq", "long.fa"}
+    for name in ("reads.fa", "reads.fq"):
+        data = golden(name)
+        assert (hashlib.sha256(data).hexdigest(), len(data)) == (inputs[name]["sha256"], inputs[name]["bytes"]), name
+    path = str(tmp_path / "long.fa")
+    got = kn_large.write_long_fasta(path, golden("reads.fa"))
+    assert got == (inputs["long.fa"]["sha256"], inputs["long.fa"]["bytes"])
+    assert kn_large.sha256_file(path) == got
+    with open(path, "rb") as f:
+        head = f.read(8)
+    assert head == b">long0\n" + head[7:8] and head[7:8] in b"ACGTN"
+    assert got[1] == sum(kn_large.LONG_LENGTHS) + 2 * (len(">long0") + 2)
