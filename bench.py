@@ -12,15 +12,23 @@ B=2G, H=4" (30 Mbp genome, 50x, 0.5 % substitution errors); --config 2 / 3 selec
 (200 M pairs, B=40G) / configs[3] (-k96 -K32).  With --gpus N (one process per GPU; run without a
 launcher, bench.py starts its N ranks itself) ONE job is split over the ranks -- by default
 configs[2], the configuration BASELINE.json lists for the partitioned filter, strong-scaled
-("scaling": "strong"; its one-GPU point is replayed from profiles/ in `strong_scaling`): every rank
-holds 1/N of the reads, the counting filter is range-partitioned by position over the ranks' HBM
-during PASS 1 (RCCL), gathered for PASS 2, whose walks are split over the ranks and merged before the
-ordered commit; the unitigs are bit-identical to a 1-GPU run of that job.
+("scaling": "strong"; its one-GPU point, in `strong_scaling`, is measured with --full, else replayed
+from profiles/): every rank holds 1/N of the reads, the counting filter is range-partitioned by
+position over the ranks' HBM during PASS 1 (RCCL), gathered for PASS 2, whose walks are split over the
+ranks and merged before the ordered commit; the unitigs are bit-identical to a
+1-GPU run of that job.
 --scaling weak makes the job N times --pairs / --bloom instead; --mode replicas runs N independent
 copies of the job (no collective on the data path).  --config 4 is configs[4] (1.2 G pairs, k=96, B=500G
 on eight GPUs): a filter beyond one GPU -- each rank keeps its own range of the counters, PASS 2 probes
 the all-gathered bit plane (abg_params.slice_filter; --slice-filter forces it at any size) -- and each
 pass is fed its reads in --chunks all-gathered pieces, so that no rank holds the read set.
+
+A run does what its headline figure needs: it generates the reads, warms up, times the steps, checks
+their unitig count and length against the reference's (tests/golden/full_size.json), writes
+--dump-outputs and prints the line.  --full adds the legs that take runs of their own: the same steps
+again without HIP events (`no_events`), the unmodified reference on a host sample (`cpu_baseline`),
+the drop-in binaries end to end on the read set's FASTQ files (`end_to_end`) and, strong-scaled over
+N > 1 ranks, the job's one-GPU point measured by rank 0 (`strong_scaling`).
 
 Prints ONE JSON line on rank 0 (see the driver contract in the task statement).
 """
@@ -314,9 +322,13 @@ def main() -> int:
     ap.add_argument("--k", type=int, default=None)
     ap.add_argument("--bloom", type=str, default=None)
     ap.add_argument("--K", type=int, default=None, help="spaced seed of two K-mers (-K of abyss-bloom-dbg)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs the headline figure does not need: after the timed steps, the steps again without HIP "
+                         "events, the CPU baseline and the drop-in binaries end to end; before them, in strong-scaled N > 1 runs, the "
+                         "job's one-GPU point")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-end-to-end", dest="end_to_end", action="store_false",
-                    help="skip the drop-in binary's FASTQ-in / FASTA-out run on this read set (about 20 s: writes the two FASTQ files)")
+                    help="--full: skip the drop-in binary's FASTQ-in / FASTA-out run on this read set (about 20 s: writes the two FASTQ files)")
     ap.add_argument("--invariants", action="store_true",
                     help="after the timed steps, add digests of the last step's device state to the line (popcounts of the counting filter, "
                          "sha256 of the counting and the visited filter, read and unitig counters): what two runs of one workload -- "
@@ -340,7 +352,7 @@ def main() -> int:
                     help="partitioned runs: each rank keeps its own range of the counting filter only (abg_params.slice_filter = 1; "
                          "without the flag the library decides by the device's memory)")
     ap.add_argument("--no-one-gpu-point", dest="one_gpu_point", action="store_false",
-                    help="strong-scaled N > 1 runs: do not measure the one-GPU point of the same job in this run (rank 0 alone, one warm-up "
+                    help="--full, strong-scaled N > 1 runs: do not measure the one-GPU point of the same job in this run (rank 0 alone, one warm-up "
                          "and one timed step before the partitioned steps: about two minutes for configs[2]); the point on file is replayed instead")
     ap.add_argument("--comm", choices=["rccl", "staged"], default="rccl",
                     help="partitioned mode: the library's RCCL communicator, or torch.distributed on host copies (diagnosis)")
@@ -444,11 +456,11 @@ def main() -> int:
             comm_note = "rccl communicator failed its self-test: replicas instead"
             a.pairs, bloom_bytes, a.bloom = single
             genome_len = int(a.pairs * 2 * read_len / cov)
-    # The one-GPU point of THIS job, measured in THIS run: rank 0 alone, the whole read set, the plain (unpartitioned) engine, one
-    # warm-up and one timed step; the other ranks wait.  (A driver that divides the N-GPU value by N times ITS one-GPU line --
+    # --full: the one-GPU point of THIS job, measured in THIS run: rank 0 alone, the whole read set, the plain (unpartitioned) engine,
+    # one warm-up and one timed step; the other ranks wait.  (A driver that divides the N-GPU value by N times ITS one-GPU line --
     # configs[1] by default -- compares two workloads: `scaling_base` below says which job the N-GPU value belongs to.)
     one_gpu = None
-    if partitioned and world > 1 and a.scaling == "strong" and a.one_gpu_point and bloom_bytes <= (100 << 30):
+    if partitioned and world > 1 and a.scaling == "strong" and a.full and a.one_gpu_point and bloom_bytes <= (100 << 30):
         if rank == 0:
             try:
                 t_g = time.perf_counter()
@@ -584,10 +596,10 @@ def main() -> int:
                   "ok": bool(unitigs == golden["unitigs"] and bases == golden["unitig_bp"])}
         if not parity["ok"] and rank == 0:
             sys.stderr.write("bench.py: PARITY FAILURE: %r\n" % (parity,))
-    # the same steps without a HIP event pair (and its host synchronisation) around every launch: what the
+    # --full: the same steps without a HIP event pair (and its host synchronisation) around every launch: what the
     # library achieves when nobody is measuring its kernels
     no_events = None
-    if timed_profile and not a.no_events and world == 1:
+    if a.full and timed_profile and not a.no_events and world == 1:
         k2 = max(1, min(a.steps, 3))
         barrier()
         t1 = time.perf_counter()
@@ -743,7 +755,7 @@ def main() -> int:
             out["kernel_ms_note"] = "rank 0, last warm-up step (the timed steps run without per-launch events)"
         if comm_note:
             out["config"]["note"] = comm_note
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.k, cores=os.cpu_count() or 1, K=a.K)
             # like for like on the FULL read set: the unmodified reference at -j<all cores> is a 4-6 minute run, measured once on a
             # GPU box's host ON THE READ SET TIMED HERE (tools/gpu_cpu_reference_full.sh) and REPLAYED from the committed file
@@ -769,7 +781,7 @@ def main() -> int:
                                  "visited_sha256": hashlib.sha256(vis).hexdigest(),
                                  "assembly_counters": {k: int(v) for k, v in c.items()}}
             del vis
-        if world == 1 and a.end_to_end and a.config in (1, 3):
+        if a.full and world == 1 and a.end_to_end and a.config in (1, 3):
             # (the binaries run as processes of their own: this process lets go of its ~27 GB of the device first -- they are timed as a
             # user would run them, not beside another tenant of the GPU)
             if g is not None:

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Evidence at the head of round 4: the whole GPU suite, the default bench line as the driver runs it, a no-events line, the
+# Evidence at the head of round 4: the whole GPU suite, the default bench line with all its legs (--full), a no-events line, the
 # rocprofv3 kernel statistics of two steps.  -> gpurun_out/r4f/
 set -u
 R=$GRAFT_REPO_ROOT
@@ -8,7 +8,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 cd $R
 timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 timeout 300 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-end-to-end --no-events > $O/bench_noevents.json 2> $O/bench_noevents.err
 python - <<'PY'
 import json
