@@ -120,8 +120,9 @@ KN_CHECK = os.path.join(ROOT, "tests", "hostcheck", "kn_check")
 
 
 def build_hostcheck(force: bool = False) -> str:
-    src = os.path.join(ROOT, "tests", "hostcheck", "hostcheck.cc")
-    if force or _newer(HOSTCHECK, [src] + csrc_files()):
+    # (hostcheck_ext.cc includes hostcheck.cc and adds the entry points written after it)
+    src = os.path.join(ROOT, "tests", "hostcheck", "hostcheck_ext.cc")
+    if force or _newer(HOSTCHECK, [src, os.path.join(ROOT, "tests", "hostcheck", "hostcheck.cc")] + csrc_files()):
         _run(["g++", "-std=c++17", "-O2", "-g", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-o", HOSTCHECK, src])
     rsrc = os.path.join(ROOT, "tests", "hostcheck", "reader_check.cc")
     if force or _newer(READER_CHECK, [rsrc, os.path.join(CSRC, "host", "fasta_reader.h")]):

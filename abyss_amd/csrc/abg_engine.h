@@ -83,6 +83,11 @@ struct Config {
 	bool memo = true;
 	uint32_t p2_max_candidates = 1u << 18; // a batch is cut after this many candidates
 	uint32_t t_tags = 1024;           // passes of the parallel commit between two clearings of its time stamps
+	uint32_t commit_incremental = 1;  // a pass of the parallel commit after the first re-stamps only what the pass before moved (Engine::commit_par):
+	                                  // 0 never, 1 where there is a stamp per filter bit, 2 with hashed stamps too (exact there as well, but not yet
+	                                  // measured at the size where stamps are hashed: DESIGN.md 4.3)
+	uint32_t commit_dirty_max = 4096; // ... unless more records than this moved a stamp (8192 at most): then a full pass
+	uint32_t commit_dirty_log2 = 26;  // ... bits of the map of the moved stamps' positions (PcDirty), at most; a filter no larger is mapped bit for bit
 	uint32_t guide_stride = 4;        // every guide_stride-th read guides the walkers' bulk steps (0: no guide, see Guide).  (8 halves guide_build, 27 -> 14 ms, and gives it back: 5x the unguided steps, rewalk +13 ms; 16: +60 ms)
 	uint32_t guide_log2_max = 31;     // at most this many guide slots (8 bytes each)
 	bool guide_seen = true;           // the bulk steps keep what they found out about a read's k-mers for the next walker (Guide::seen)
@@ -2139,6 +2144,28 @@ struct FDupVerify { // one wave per record: the link holds only if the two hash 
 // -- every rank holds the whole visited filter, but the tests are random reads and R ranks would
 // each make all of them -- and leaves one byte per candidate (part_c) and per record (part_r,
 // indexed like recs) that an all_reduce(MIN) turns into the verdicts; FPreCommitFin applies them.
+// "test(j) holds for every k-mer j < n", by one wave (nlanes == 64) or one serial caller (nlanes == 1).  Where the answer is
+// "no" it is usually plain from the start -- a contig is either committed already or not at all, and a read that is not
+// visited has few visited k-mers -- so the first nlanes k-mers are tested and voted on by themselves, and the rest, PC_SCAN_RUN
+// chunks between two votes, only while every k-mer so far passed.  The exits are the wave's, never a lane's: within a run
+// every lane issues its loads whatever its own verdict.  first_chunk: the first vote settled it.
+constexpr uint32_t PC_SCAN_RUN = 4;
+template <class Test>
+ABG_HD bool wave_all_kmers(uint32_t n, uint32_t lane, uint32_t nlanes, Test test, bool& first_chunk)
+{
+	bool mine = lane < n ? test(lane) : true;
+	first_chunk = !wave_all_lanes(mine, nlanes);
+	if (first_chunk) return false;
+	for (uint32_t j0 = nlanes; j0 < n; j0 += PC_SCAN_RUN * nlanes) {
+#pragma unroll
+		for (uint32_t u = 0; u < PC_SCAN_RUN; u++) {
+			const uint32_t j = j0 + u * nlanes + lane;
+			if (j < n) mine = mine & test(j);
+		}
+		if (!wave_all_lanes(mine, nlanes)) return false;
+	}
+	return true;
+}
 ABG_HD bool visited_contains_owned(const Params& p, const uint8_t* __restrict__ vis, uint64_t h, uint64_t lo, uint64_t span)
 {
 	bool ok = true;
@@ -2162,14 +2189,17 @@ struct FPreCommit {
 	ContigRec* recs; const uint8_t* vis; const uint64_t* kh; const uint64_t* rkh; const uint64_t* rkoff;
 	uint8_t* read_flag; uint32_t first;
 	uint64_t lo, span; uint8_t* part_c; uint8_t* part_r; // (whole filter: 0, ~0, NULL, NULL)
+	uint32_t* nfirst; // [candidates of the call] tests that their first chunk of k-mers settled (statistics), or NULL
 	ABG_HDN void operator()(uint64_t i, uint32_t lane, uint32_t nlanes) const
 	{
 		uint32_t c = first + (uint32_t)i;
 		uint64_t r = cand_read[c];
 		uint32_t nk = b.len[r] - p.k + 1;
-		bool all = true;
-		for (uint32_t j = lane; j < nk; j += nlanes) all = all & visited_contains_owned(p, vis, rkh[rkoff[c] + j], lo, span);
-		all = wave_all_lanes(all, nlanes);
+		const uint64_t* rh = rkh + rkoff[c];
+		bool fc;
+		const bool all = wave_all_kmers(nk, lane, nlanes, [&](uint32_t j) { return visited_contains_owned(p, vis, rh[j], lo, span); }, fc);
+		uint32_t nf = fc ? 1u : 0u;
+		if (nfirst && lane == 0) nfirst[i] = nf;
 		if (part_c) {
 			if (lane == 0) part_c[i] = all ? 1 : 0;
 			if (status[c] != WS_COMPLETE) return;
@@ -2184,12 +2214,13 @@ struct FPreCommit {
 			// (a verified copy of a record this very call tests -- a lower candidate's, same k-mers, same snapshot -- takes that
 			// one's answer afterwards, FPreCommitCopies: four fifths of a batch's record k-mers are such copies)
 			if (rec.dup_of != REC_END && recs[rec.dup_of].cand >= first) continue;
-			bool red = true;
-			for (uint32_t j = lane; j < cnk; j += nlanes) red = red & visited_contains_owned(p, vis, kh[rec.seq_off + j], lo, span);
-			red = wave_all_lanes(red, nlanes);
+			const uint64_t* ch = kh + rec.seq_off;
+			const bool red = wave_all_kmers(cnk, lane, nlanes, [&](uint32_t j) { return visited_contains_owned(p, vis, ch[j], lo, span); }, fc);
+			nf += fc ? 1u : 0u;
 			if (part_r) { if (lane == 0) part_r[ri] = red ? 1 : 0; }
 			else if (lane == 0 && red) rec.pre_redundant = 1;
 		}
+		if (nfirst && lane == 0) nfirst[i] = nf;
 	}
 };
 struct FPreCommitCopies { // one candidate per item, after FPreCommit: the copies take their original's answer ("entirely visited" is a fact about the k-mer set)
@@ -2604,7 +2635,14 @@ struct ParCommit {
 	uint8_t* active;       // [n] the read is not visited at its turn
 	uint32_t* short_list;  // records of short contigs (unordered)
 	VKey* short_keys;      // [2 per entry of short_list] their canonical end k-mers (FPcShortKeys)
-	uint32_t* scal;        // [0] changed  [1] break candidate  [2] short_list length  [3] new contigEndKmers entries
+	uint32_t* scal;        // [0] changed  [1] break candidate  [2] short_list length  [3] new contigEndKmers entries  [4] contigEndKmers full
+	                       // [5] records whose change of verdict moved T in this pass  [6] their k-mers
+	uint32_t* nfirst;      // [n] "every k-mer" tests of the candidate that their first chunk settled, all passes (statistics; NULL in a partitioned run)
+	// incremental passes (Engine::commit_par): the records of [5], as far as the list has room, and the map of the positions of
+	// the bits of the previous pass's list -- a bit per filter position (A_shift == 0) or per hashed position: a position of
+	// the list is always found in the map, a position found there need not be one of the list
+	uint32_t* dirty; uint32_t dirty_cap;
+	uint32_t* A; uint32_t A_shift;
 	uint32_t c_begin, c_end, brk;
 	// partitioned run: the stamps and the bit tests of [own_lo, own_lo + own_span) only (whole filter: 0, ~0),
 	// and a byte per candidate / per record for what the ranks combine (see FPcDecideA)
@@ -2666,6 +2704,51 @@ ABG_HD bool pc_bit_before(const ParCommit& e, uint64_t h, uint32_t time)
 	}
 	return ok;
 }
+ABG_HD uint64_t pc_dirty_index(const ParCommit& e, uint64_t pos) { return e.A_shift ? (pos * 0x9E3779B97F4A7C15ULL) >> e.A_shift : pos; }
+// bit q: the position of k-mer h under hash function q is in the map of moved stamps (up to four functions: the loads together)
+ABG_HD uint32_t pc_dirty_mask(const ParCommit& e, uint64_t h)
+{
+	uint32_t m = 0;
+	if (e.p.nh <= 4) {
+		uint64_t a[4]; uint32_t w[4];
+#pragma unroll
+		for (unsigned q = 0; q < 4; q++) { a[q] = pc_dirty_index(e, pos_i(e.p, h, q < e.p.nh ? q : 0u)); w[q] = e.A[a[q] >> 5]; }
+#pragma unroll
+		for (unsigned q = 0; q < 4; q++) if (q < e.p.nh) m |= ((w[q] >> (a[q] & 31)) & 1u) << q;
+		return m;
+	}
+	for (unsigned q = 0; q < e.p.nh; q++) {
+		const uint64_t a = pc_dirty_index(e, pos_i(e.p, h, q));
+		m |= ((e.A[a >> 5] >> (a & 31)) & 1u) << q;
+	}
+	return m;
+}
+// Before an incremental pass (clear == 0), one wave per record of the previous pass's list: its bits' positions into the map, and
+// the stamps of those bits back to "never" -- whichever record held them; FPcTimeMin then restores, at the map's positions, the
+// minimum over the records that are inserted now.  After that (clear == 1): the map's words back to zero.
+struct FPcDirty {
+	ParCommit e; const uint32_t* list; uint32_t clear;
+	ABG_HDN void operator()(uint64_t i, uint32_t lane, uint32_t nlanes) const
+	{
+		const ContigRec& rec = e.recs[list[i]];
+		const uint64_t* ch = e.kh + rec.seq_off;
+		const uint32_t cnk = rec.len - e.p.k + 1;
+		for (uint32_t j = lane; j < cnk; j += nlanes)
+			for (unsigned q = 0; q < e.p.nh; q++) {
+				const uint64_t pos = pos_i(e.p, ch[j], q);
+				const uint64_t a = pc_dirty_index(e, pos);
+				if (clear) { e.A[a >> 5] = 0; continue; }
+				atomic_or_u32(&e.A[a >> 5], 1u << (a & 31));
+				if (e.T) { e.T[pos] = T_NEVER; continue; }
+				// (hashed stamps: the key stays, and a position never stamped has none)
+				for (uint64_t s = pc_T_hash(e, pos);; s = (s + 1) & e.Tmask) {
+					const uint64_t cur = e.Tk[s];
+					if (cur == pos) { e.Tv[s] = T_NEVER; break; }
+					if (cur == T_KEY_EMPTY) break;
+				}
+			}
+	}
+};
 struct FPcCount { // records of each candidate whose walk completed
 	ParCommit e;
 	ABG_HD void operator()(uint64_t i, uint32_t) const
@@ -2707,8 +2790,8 @@ struct FPcSnapshot { // ins as the pass before left it (the copies of a contig d
 		for (uint32_t ri = e.first_rec[c]; ri != REC_END; ri = e.recs[ri].next) e.recs[ri].ins_prev = e.recs[ri].ins;
 	}
 };
-struct FPcTimeMin { // T: one wave per candidate
-	ParCommit e;
+struct FPcTimeMin { // T: one wave per candidate.  inc: an incremental pass -- only the stamps at the positions of the map (FPcDirty)
+	ParCommit e; uint32_t inc;
 	ABG_HDN void operator()(uint64_t i, uint32_t lane, uint32_t nlanes) const
 	{
 		uint32_t c = e.c_begin + (uint32_t)i;
@@ -2720,7 +2803,10 @@ struct FPcTimeMin { // T: one wave per candidate
 			const uint32_t cnk = rec.len - e.p.k + 1;
 			for (uint32_t j = lane; j < cnk; j += nlanes) {
 				uint64_t h = ch[j];
+				const uint32_t which = inc ? pc_dirty_mask(e, h) : ~0u;
+				if (!which) continue;
 				for (unsigned q = 0; q < e.p.nh; q++) {
+					if (!((which >> q) & 1u)) continue;
 					const uint64_t pos = pos_i(e.p, h, q);
 					if (pos - e.own_lo < e.own_span) atomic_min_u32(pc_T_slot(e, pos), t_stamp(e.tag, rec.time));
 				}
@@ -2781,23 +2867,42 @@ ABG_HD bool pc_end_before(const ParCommit& e, const VKey& key, uint32_t time)
 	uint64_t s = wt_find(e.tcend, key, 0);
 	return s != WT_EMPTY && e.tcend.meta[s] < (uint64_t)time;
 }
-struct FPcDecide { // one wave per candidate: re-decide the read and its contigs against T
+// "no unset bit of the contig carries the contig's own position": a change of its verdict then leaves T as it is where it matters
+template <class E>
+ABG_HD bool pc_owns_no_unset_bit(const E& e, const ContigRec& rec, uint32_t lane, uint32_t nlanes, bool owned_only)
+{
+	const uint64_t* ch = e.kh + rec.seq_off;
+	const uint32_t cnk = rec.len - e.p.k + 1;
+	bool fc;
+	return wave_all_kmers(cnk, lane, nlanes, [&](uint32_t j) {
+		bool own = false;
+		for (unsigned q = 0; q < e.p.nh; q++) {
+			uint64_t pos = pos_i(e.p, ch[j], q);
+			if (owned_only && pos - e.own_lo >= e.own_span) continue;
+			own = own | (t_read(pc_T_get(e, pos), e.tag) == rec.time && !((e.vis32[pos >> 5] >> (pos & 31)) & 1u));
+		}
+		return !own; }, fc);
+}
+// One wave per candidate: re-decide the read and its contigs against T -- the same in a full and in an incremental pass
+// (Engine::commit_par): the tests that fail do so in their first chunk, and the ones that hold are few.
+struct FPcDecide {
 	ParCommit e;
 	ABG_HDN void operator()(uint64_t i, uint32_t lane, uint32_t nlanes) const
 	{
 		const uint32_t c = e.c_begin + (uint32_t)i;
 		const unsigned k = e.p.k;
 		bool visited = e.read_flag[c] != 0;
+		bool fc;
+		uint32_t nf = 0;
 		if (!visited) {
 			const uint32_t nk = e.b.len[e.cand_read[c]] - k + 1;
 			const uint64_t* rh = e.rkh + e.rkoff[c];
 			const uint32_t t0 = e.off[i];
-			bool mine = true;
-			for (uint32_t j = lane; j < nk; j += nlanes) mine = mine & pc_bit_before(e, rh[j], t0);
-			visited = wave_all_lanes(mine, nlanes);
+			visited = wave_all_kmers(nk, lane, nlanes, [&](uint32_t j) { return pc_bit_before(e, rh[j], t0); }, fc);
+			nf += fc ? 1u : 0u;
 		}
 		if (lane == 0) e.active[i] = visited ? 0 : 1;
-		if (e.status[c] != WS_COMPLETE) return;
+		if (e.status[c] != WS_COMPLETE) { if (nf && lane == 0 && e.nfirst) e.nfirst[i] += nf; return; }
 		bool changed = false;
 		for (uint32_t ri = e.first_rec[c]; ri != REC_END; ri = e.recs[ri].next) {
 			ContigRec& rec = e.recs[ri];
@@ -2816,37 +2921,35 @@ struct FPcDecide { // one wave per candidate: re-decide the read and its contigs
 				} else {
 					const uint64_t* ch = e.kh + rec.seq_off;
 					const uint32_t cnk = rec.len - k + 1;
-					bool mine = true;
-					for (uint32_t j = lane; j < cnk; j += nlanes) mine = mine & pc_bit_before(e, ch[j], rec.time);
-					red = wave_all_lanes(mine, nlanes);
+					red = wave_all_kmers(cnk, lane, nlanes, [&](uint32_t j) { return pc_bit_before(e, ch[j], rec.time); }, fc);
+					nf += fc ? 1u : 0u;
 				}
 				ins = red ? 0u : 1u;
 			}
 			// Does the change move T?  A long contig dropped because all its bits were set earlier
 			// was not the earliest setter of any bit that matters, and neither is a contig of a
 			// skipped read unless some unset bit carries its own position: then T, and with it every
-			// other decision, stays as it is.  Anything else calls for another pass.
+			// other decision, stays as it is.  Anything else calls for another pass, and goes on the list
+			// of what that pass has to look at.
 			if (ins != rec.ins) {
 				bool moves = true;
 				if (rec.ins && rec.len >= k + FP_TRIM - 1) {
 					moves = false;
-					if (visited) {
-						const uint64_t* ch = e.kh + rec.seq_off;
-						const uint32_t cnk = rec.len - k + 1;
-						bool mine = false;
-						for (uint32_t j = lane; j < cnk; j += nlanes)
-							for (unsigned q = 0; q < e.p.nh; q++) {
-								uint64_t pos = pos_i(e.p, ch[j], q);
-								mine = mine | (t_read(pc_T_get(e, pos), e.tag) == rec.time && !((e.vis32[pos >> 5] >> (pos & 31)) & 1u));
-							}
-						moves = !wave_all_lanes(!mine, nlanes);
-					}
+					if (visited) moves = !pc_owns_no_unset_bit(e, rec, lane, nlanes, false);
 				}
 				changed = changed | moves;
+				if (moves && lane == 0) {
+					const uint32_t q = atomic_add_u32(&e.scal[5], 1);
+					atomic_add_u32(&e.scal[6], rec.len - k + 1 < (1u << 18) ? rec.len - k + 1 : 1u << 18); // (8192 of them fit the word)
+					if (q < e.dirty_cap) e.dirty[q] = ri;
+				}
 			}
 			if (lane == 0) rec.ins = ins;
 		}
-		if (changed && lane == 0) e.scal[0] = 1;
+		if (lane == 0) {
+			if (nf && e.nfirst) e.nfirst[i] += nf;
+			if (changed) e.scal[0] = 1;
+		}
 	}
 };
 // ---- FPcDecide of a partitioned run, in three steps around two small all_reduces.  A: every rank
@@ -2860,14 +2963,12 @@ struct FPcDecideA {
 	{
 		const uint32_t c = e.c_begin + (uint32_t)i;
 		const unsigned k = e.p.k;
-		bool pv = true;
+		bool pv = true, fc;
 		if (!e.read_flag[c]) {
 			const uint32_t nk = e.b.len[e.cand_read[c]] - k + 1;
 			const uint64_t* rh = e.rkh + e.rkoff[c];
 			const uint32_t t0 = e.off[i];
-			bool mine = true;
-			for (uint32_t j = lane; j < nk; j += nlanes) mine = mine & pc_bit_before(e, rh[j], t0);
-			pv = wave_all_lanes(mine, nlanes);
+			pv = wave_all_kmers(nk, lane, nlanes, [&](uint32_t j) { return pc_bit_before(e, rh[j], t0); }, fc);
 		}
 		if (lane == 0) e.part_c[i] = pv ? 1 : 0;
 		if (e.status[c] != WS_COMPLETE) return;
@@ -2876,9 +2977,7 @@ struct FPcDecideA {
 			if (rec.len < k + FP_TRIM - 1 || rec.pre_redundant) continue;
 			const uint64_t* ch = e.kh + rec.seq_off;
 			const uint32_t cnk = rec.len - k + 1;
-			bool mine = true;
-			for (uint32_t j = lane; j < cnk; j += nlanes) mine = mine & pc_bit_before(e, ch[j], rec.time);
-			mine = wave_all_lanes(mine, nlanes);
+			const bool mine = wave_all_kmers(cnk, lane, nlanes, [&](uint32_t j) { return pc_bit_before(e, ch[j], rec.time); }, fc);
 			if (lane == 0) e.part_r[ri] = mine ? 1 : 0;
 		}
 	}
@@ -2911,18 +3010,7 @@ struct FPcDecideB {
 				}
 				if (ins != rec.ins) {
 					if (rec.ins && rec.len >= k + FP_TRIM - 1) {
-						if (visited) {
-							const uint64_t* ch = e.kh + rec.seq_off;
-							const uint32_t cnk = rec.len - k + 1;
-							bool mine = false;
-							for (uint32_t j = lane; j < cnk; j += nlanes)
-								for (unsigned q = 0; q < e.p.nh; q++) {
-									uint64_t pos = pos_i(e.p, ch[j], q);
-									if (pos - e.own_lo >= e.own_span) continue;
-									mine = mine | (t_read(pc_T_get(e, pos), e.tag) == rec.time && !((e.vis32[pos >> 5] >> (pos & 31)) & 1u));
-								}
-							moved_here = moved_here | !wave_all_lanes(!mine, nlanes);
-						}
+						if (visited) moved_here = moved_here | !pc_owns_no_unset_bit(e, rec, lane, nlanes, true);
 					} else {
 						changed = true;
 					}
@@ -3121,6 +3209,7 @@ class Engine {
 		if (mask_d_) be_.free(mask_d_);
 		if (T_) be_.free(T_);
 		if (Tk_) { be_.free(Tk_); be_.free(Tv_); }
+		if (pcA_) be_.free(pcA_);
 		if (la_pool_c_) be_.free(la_pool_c_);
 		if (la_pool_c2_) be_.free(la_pool_c2_);
 		if (guide_tab_) be_.free(guide_tab_);
@@ -3722,7 +3811,8 @@ class Engine {
 	}
 	struct Stats { uint64_t rounds = 0, walked = 0, rewalked = 0, candidates = 0, breaks = 0, insert_rounds = 0, commit_rounds = 0, generated = 0;
 	               uint64_t bulk_calls = 0, bulk_steps = 0, lin_steps = 0, guide_slots = 0, chain_steps = 0, batch_cuts = 0, overflows = 0, memo_hits = 0, memo_adds = 0;
-	               uint64_t tiled_ops = 0, tiled_pending = 0, tile_overflows = 0, cls_covered_reads = 0, archive_bases = 0, cls_decided_reads = 0; };
+	               uint64_t tiled_ops = 0, tiled_pending = 0, tile_overflows = 0, cls_covered_reads = 0, archive_bases = 0, cls_decided_reads = 0;
+	               uint64_t commit_rounds_incremental = 0, commit_dirty_records = 0, commit_first_chunk_decided = 0; };
 	Stats stats()
 	{
 		Stats s = stats_;
@@ -3756,6 +3846,8 @@ class Engine {
 	// switched off) the ordered single-workgroup kernel runs
 	uint64_t* Tk_ = nullptr; uint32_t* Tv_ = nullptr; uint32_t Tlog2_ = 0; // ... or per touched bit (see pc_T_slot)
 	uint64_t T_entries_ = 0; // upper bound of the keys in the table
+	uint32_t* pcA_ = nullptr; uint64_t pcA_bits_ = 0; uint32_t pcA_shift_ = 0; // incremental passes: the map of moved stamps (ParCommit::A), all zero between passes;
+	                                                                           // sized once, at the first incremental commit: m_ and cfg_ are fixed at construction
 	bool t_hashed() const { return t_force_hashed_ || m_ * 4ull > cfg_.par_commit_max_bytes; }
 	bool t_force_hashed_ = false; // no room for a stamp per filter bit on a sliced filter, where the ordered kernel cannot run: a stamp per touched bit
 	bool use_par_commit()
@@ -4646,7 +4738,7 @@ class Engine {
 		cs.break_at = c_begin; cs.pad_ = 0; cs.cend_count = cend_count_;
 		be_.h2d(cstate_, &cs, sizeof cs);
 		{
-			FPreCommit<NW> f{ p_, b, cand_d, status_d, first_d, recs_, vis_, kh_, rkh_, rkoff_d, read_flag_, c_begin, 0, ~0ULL, nullptr, nullptr };
+			FPreCommit<NW> f{ p_, b, cand_d, status_d, first_d, recs_, vis_, kh_, rkh_, rkoff_d, read_flag_, c_begin, 0, ~0ULL, nullptr, nullptr, nullptr };
 			be_.launch_wave(c_end - c_begin, f, "precommit");
 			FPreCommitCopies fc{ status_d, first_d, recs_, read_flag_, c_begin, p_.k };
 			be_.launch(c_end - c_begin, fc, "precommit");
@@ -4687,10 +4779,13 @@ class Engine {
 		const bool part = dist();
 		uint8_t* part_buf = part ? (uint8_t*)be_.alloc((uint64_t)n + nrec + 64) : nullptr;
 		uint8_t* part_c = part_buf; uint8_t* part_r = part ? part_buf + n : nullptr;
+		// (statistics of plain runs only: a rank of a partitioned run tests its own bits, and the ranks' statistics are compared)
+		uint32_t* nfirst = part ? nullptr : (uint32_t*)be_.alloc(n * 4ull + 4);
+		if (nfirst) be_.memset(nfirst, 0, n * 4ull);
 		{
 			if (part) be_.memset(part_buf, 1, (uint64_t)n + nrec);
 			FPreCommit<NW> f{ p_, b, cand_d, status_d, first_d, recs_, vis_, kh_, rkh_, rkoff_d, read_flag_, c_begin,
-				part ? own_lo_ : 0, part ? own_span_ : ~0ULL, part_c, part_r };
+				part ? own_lo_ : 0, part ? own_span_ : ~0ULL, part_c, part_r, nfirst };
 			be_.launch_wave(n, f, "precommit");
 			if (!part) { FPreCommitCopies fc{ status_d, first_d, recs_, read_flag_, c_begin, p_.k }; be_.launch(n, fc, "precommit"); }
 			if (part) {
@@ -4735,6 +4830,25 @@ class Engine {
 		e.scal = (uint32_t*)be_.alloc(64);
 		uint32_t scal_h[8] = { 0, 0xFFFFFFFFu, 0, 0, 0, 0, 0, 0 };
 		be_.h2d(e.scal, scal_h, sizeof scal_h);
+		e.nfirst = nfirst;
+		// incremental passes: two lists of moved records (one is read while the other fills) and the map of their bits' positions
+		const bool incremental = cfg_.commit_incremental && (cfg_.commit_incremental > 1 || !t_hashed()) && !part && cfg_.commit_dirty_max > 0 && nrec > 0;
+		uint32_t* dirty_buf = nullptr;
+		e.dirty = nullptr; e.dirty_cap = 0; e.A = nullptr; e.A_shift = 0;
+		if (incremental) {
+			e.dirty_cap = (uint32_t)std::min<uint64_t>(std::min(cfg_.commit_dirty_max, 8192u), std::max(nrec, 1u));
+			dirty_buf = (uint32_t*)be_.alloc(2ull * e.dirty_cap * 4 + 8);
+			e.dirty = dirty_buf;
+			if (!pcA_) {
+				// (a word more than the bits: the map is left all zero by every pass that used it)
+				const uint32_t log2 = std::min(34u, std::max(10u, cfg_.commit_dirty_log2));
+				pcA_bits_ = std::min<uint64_t>(m_, 1ull << log2);
+				pcA_shift_ = pcA_bits_ < m_ ? 64 - log2 : 0;
+				pcA_ = (uint32_t*)be_.alloc((pcA_bits_ + 31) / 32 * 4 + 4);
+				be_.memset(pcA_, 0, (pcA_bits_ + 31) / 32 * 4 + 4);
+			}
+			e.A = pcA_; e.A_shift = pcA_shift_;
+		}
 		e.tcend = WalkTab{ nullptr, nullptr, nullptr, 0 };
 		// commit positions
 		std::vector<uint32_t> c1(n), c2(n), off(n + 1ull);
@@ -4763,25 +4877,47 @@ class Engine {
 			FPcShortKeys f{ e };
 			be_.launch(nshort, f, "pc_short_keys");
 		}
-		// the fixed point
+		// The fixed point.  A pass after the first is INCREMENTAL where it can be.  What the pass before left: T = the minimum over the
+		// records inserted BEFORE it (ins_prev), and the list D of the records whose verdict it changed in a way that moves T
+		// (FPcDecide).  A full pass would take a new tag -- voiding every stamp --, stamp every inserted record and decide everything
+		// anew.  The incremental one keeps the tag, sets the stamps at the bits of D's records back to "never" and notes those bits'
+		// positions in the map A (FPcDirty), lets every inserted record lower the stamps at A's positions only (FPcTimeMin) --
+		// so T is, at every bit of D, the minimum over the records inserted now, and elsewhere what it was --, clears the map and
+		// decides (FPcDecide) exactly as a full pass does.  Exactness: a verdict is a function of the
+		// filter, of T at the record's own bits, for a copy of its original's ins_prev and for a short contig of the end k-mers of
+		// the inserted short ones (rebuilt every pass, as before).  The full pass's T differs from the kept one only where a record
+		// that is no longer inserted left a stamp without being in D: by FPcDecide's argument that stamp is the minimum of no bit
+		// that is unset, so no test reads it differently.  Where A holds a position it need not (hashed positions collide) a stamp is
+		// lowered to the value it has.  Hence ins after the pass is what the full pass
+		// computes, every iterate is the same and so is the number of passes.
+		// A full pass is taken when D did not fit its list or would crowd A (an eighth of its bits), when the tags ran out, in a
+		// partitioned run and with ABG_COMMIT_INCREMENTAL=0.
+		uint32_t nd = 0, nd_kmers = 0, fill = 0; // D of the pass before: records, their k-mers, which half of dirty_buf holds them
 		for (uint32_t round = 0;; round++) {
-			// (tag T_TAGS - 1 is what the cleared array carries: never handed out; cfg_.t_tags < T_TAGS only
-			// makes the clearing more frequent -- the tests use that to exercise it)
-			if (t_tag_ == 0) {
-				// the tags ran out: every stamp back to "never" (a hashed table keeps its keys)
-				if (e.T) be_.memset(e.T, 0xFF, m_ * 4ull);
-				else be_.memset(e.Tv, 0xFF, 4ull << Tlog2_);
-				t_tag_ = std::min<uint32_t>(cfg_.t_tags, T_TAGS) - 1;
-			}
-			e.tag = --t_tag_;
+			const bool inc = round && incremental && t_tag_ != 0 && nd <= e.dirty_cap && (uint64_t)nd_kmers * p_.nh * 8 <= pcA_bits_;
+			const uint32_t* list = dirty_buf ? dirty_buf + (size_t)fill * e.dirty_cap : nullptr;
+			if (!inc) {
+				// (tag T_TAGS - 1 is what the cleared array carries: never handed out; cfg_.t_tags < T_TAGS only
+				// makes the clearing more frequent -- the tests use that to exercise it)
+				if (t_tag_ == 0) {
+					// the tags ran out: every stamp back to "never" (a hashed table keeps its keys)
+					if (e.T) be_.memset(e.T, 0xFF, m_ * 4ull);
+					else be_.memset(e.Tv, 0xFF, 4ull << Tlog2_);
+					t_tag_ = std::min<uint32_t>(cfg_.t_tags, T_TAGS) - 1;
+				}
+				e.tag = --t_tag_;
+			} else { FPcDirty f{ e, list, 0u }; be_.launch_wave(nd, f, "pc_timemin"); }
+			if (dirty_buf) { fill ^= 1; e.dirty = dirty_buf + (size_t)fill * e.dirty_cap; }
 			if (nshort) {
 				be_.memset(e.tcend.hmin, 0xFF, (e.tcend.mask + 1) * 8);
 				FPcShort f{ e, 0 };
 				be_.launch(1, f, "pc_short");
 			}
 			be_.memset(e.scal, 0, 4);
+			be_.memset(e.scal + 5, 0, 8);
 			if (round && !part && cfg_.link_duplicates) { FPcSnapshot f{ e }; be_.launch(n, f, "pc_stamp"); }
-			{ FPcTimeMin f{ e }; be_.launch_wave(n, f, "pc_timemin"); }
+			{ FPcTimeMin f{ e, inc ? 1u : 0u }; be_.launch_wave(n, f, "pc_timemin"); }
+			if (inc) { FPcDirty f{ e, list, 1u }; be_.launch_wave(nd, f, "pc_timemin"); }
 			if (part) {
 				be_.memset(part_buf, 1, (uint64_t)n0 + nrec);
 				{ FPcDecideA f{ e }; be_.launch_wave(n, f, "pc_decide"); }
@@ -4790,8 +4926,11 @@ class Engine {
 				c_all_reduce(part_c, n, DT_U8, OP_MAX);
 				{ FPcDecideC f{ e }; be_.launch(n, f, "pc_decide"); }
 			} else { FPcDecide f{ e }; be_.launch_wave(n, f, "pc_decide"); }
-			be_.d2h(scal_h, e.scal, 4);
+			be_.d2h(scal_h, e.scal, sizeof scal_h);
 			stats_.commit_rounds++;
+			if (inc) stats_.commit_rounds_incremental++;
+			nd = scal_h[5]; nd_kmers = scal_h[6];
+			stats_.commit_dirty_records += nd;
 			if (!scal_h[0]) break;
 		}
 		{ FPcBreak f{ e }; be_.launch(n, f, "pc_break"); }
@@ -4840,6 +4979,14 @@ class Engine {
 		if (nshort) { free_tab(e.tcend); be_.free(e.short_keys); }
 		be_.free(e.off); be_.free(e.cnt); be_.free(e.cnt2); be_.free(e.cnt3); be_.free(e.active);
 		be_.free(e.short_list); be_.free(e.scal);
+		if (nfirst) {
+			// (the candidates this call commits: the ones cut off above are counted when the caller comes back with them)
+			std::vector<uint32_t> nf(n);
+			be_.d2h(nf.data(), nfirst, n * 4ull);
+			for (uint32_t v : nf) stats_.commit_first_chunk_decided += v;
+			be_.free(nfirst);
+		}
+		if (dirty_buf) be_.free(dirty_buf);
 		if (part_buf) be_.free(part_buf);
 		return brk;
 	}

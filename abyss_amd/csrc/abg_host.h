@@ -92,6 +92,9 @@ class Session {
 		if (const char* e = getenv("ABG_P2_MAX_BATCH")) cfg.p2_max_batch = strtoull(e, 0, 10);
 		if (const char* e = getenv("ABG_PAR_COMMIT")) cfg.par_commit = atoi(e) != 0;
 		if (const char* e = getenv("ABG_T_TAGS")) cfg.t_tags = (uint32_t)std::max(2, atoi(e));
+		if (const char* e = getenv("ABG_COMMIT_INCREMENTAL")) cfg.commit_incremental = (uint32_t)std::min(2, std::max(0, atoi(e))); // 0: every pass of the parallel commit is a full one; 2: incremental with hashed stamps too
+		if (const char* e = getenv("ABG_COMMIT_DIRTY_MAX")) cfg.commit_dirty_max = (uint32_t)std::max(0, atoi(e)); // records a pass may have moved for the next to be incremental (0: never; the engine takes at most 8192)
+		if (const char* e = getenv("ABG_COMMIT_DIRTY_LOG2")) cfg.commit_dirty_log2 = (uint32_t)std::min(34, std::max(10, atoi(e))); // log2 of the bits of the map of moved stamps (the engine keeps it within 10..34)
 		if (const char* e = getenv("ABG_PAR_COMMIT_MAX_GB")) cfg.par_commit_max_bytes = strtoull(e, 0, 10) << 30; // e.g. 160 for B=40G on a 288 GB GPU
 		if (const char* e = getenv("ABG_COMPACT_THRESHOLD")) cfg.compact_threshold = strtoull(e, 0, 10);
 		if (const char* e = getenv("ABG_TILED")) cfg.tiled_insert = atoi(e) != 0; // PASS 1 through LDS tiles

@@ -1210,6 +1210,8 @@ int abg_get_stats(const abg_ctx* ctx, abg_stats* out)
 		out->tiled_ops = s.tiled_ops; out->tiled_pending = s.tiled_pending; out->tile_overflows = s.tile_overflows;
 		out->cls_covered_reads = s.cls_covered_reads; out->archive_bases = s.archive_bases; out->cls_decided_reads = s.cls_decided_reads;
 		out->counter_bytes_held = ctx->s.eng->counter_bytes_held();
+		out->commit_rounds_incremental = s.commit_rounds_incremental; out->commit_dirty_records = s.commit_dirty_records;
+		out->commit_first_chunk_decided = s.commit_first_chunk_decided;
 		return ABG_OK;
 	});
 }

@@ -336,6 +336,9 @@ typedef struct abg_stats {
 	uint64_t archive_bases; /* ... bytes of that archive in use (until round 6: pre_adds, always 0) */
 	uint64_t cls_decided_reads; /* ... of which this many got their whole verdict there, both look-aheads included (until round 6: cancelled, always 0) */
 	uint64_t counter_bytes_held; /* bytes of the counting filter this context holds: all of it, or its own range of a sliced filter (abg_params.slice_filter) */
+	uint64_t commit_rounds_incremental; /* ... of commit_rounds: passes that re-stamped and re-decided only what the pass before had moved */
+	uint64_t commit_dirty_records;      /* contig records whose change of verdict moved a time stamp and so called for another pass, summed over the passes */
+	uint64_t commit_first_chunk_decided; /* parallel commit, plain (not partitioned) runs: contigs and reads whose "every k-mer visited" test failed within its first chunk of k-mers */
 } abg_stats;
 int abg_get_stats(const abg_ctx* ctx, abg_stats* out);
 
