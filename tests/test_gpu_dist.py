@@ -5,13 +5,18 @@
   kernels (FHashClaimT<true>, FEvalDist / FApplyDist, the hipcub compaction, the drain hand-over,
   the split classification and the merge of walk results) and every RCCL call (ncclAllReduce,
   in-place ncclAllGather) run on the device, each collective an identity;
-* two and three ranks sharing the GPU, joined by gloo through host copies.
+* two and three ranks sharing the GPU, joined by gloo through host copies;
+* two to eight ranks sharing the GPU on the inputs of the CPU suite's hard cases (tests/dist_cases.py: a commit that needs
+  a second pass, saturating counters, tile and route overflow, kept reads, spaced seeds, routing over uneven owner ranges),
+  one launch per world size.
 
-Both must reproduce the reference's single sequential run bit for bit, and exit cleanly."""
+All must reproduce the reference's single sequential run bit for bit, and exit cleanly."""
 import json
 import os
+import re
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -119,6 +124,150 @@ def test_bench_runs_configs4_scaled_down_on_two_ranks():
     assert d["n_gpus"] == 2 and c["ranks_agree"] is True and c["chunks"] == 3 and "k=96" in c["workload"], c
     assert 0 < c["counter_bytes_per_rank"] < 0.51 * (120 << 20) / 1.125 + 4096, c
     assert c["unitigs"] > 1000 and d["value"] > 0
+
+
+# ---- the CPU suite's hard cases (tests/test_dist_partition.py) with the real kernels: tests/dist_gpu_worker.py `cases` ----
+# world -> the cases of its one launch, as the worker's SPECs (case[+arg][:ENV=VAL,...]; route = ABG_DIST_ROUTE_MIN)
+LAUNCHES = {
+    2: ["oracle:ABG_TILE_CAP=300", "oracle:ABG_TILED=0", "golden+k48_K16:route=2", "golden+s_mixed_k32_H12_kc3"],
+    3: ["bigbatch:route=0", "bigbatch:route=0,ABG_PAR_COMMIT_MAX_GB=0,ABG_T_TAGS=5", "tiny_filter:route=0", "saturate", "saturate_tiled:route=2",
+        "oracle:route=2,ABG_ROUTE_CAP=500", "sliced_checkpoint:ABG_SLICE_FILTER=1", "golden+s_tandem_k32"],
+    # (from four ranks on the pairs are routed by default)
+    4: ["oracle", "bigbatch", "tiny_filter", "saturate_tiled", "kept", "shared", "golden+k64:ABG_SLICE_FILTER=1",
+        "sliced:ABG_SLICE_FILTER=1,ABG_ROUTE_CAP=64", "bigbatch:ABG_SLICE_FILTER=1,ABG_PAR_COMMIT_MAX_GB=0,ABG_T_TAGS=5"],
+    5: ["tiny_filter", "golden+s_mixed_k40_H6", "shared"],
+    8: ["golden+k32", "bigbatch", "sliced+shared:ABG_SLICE_FILTER=1"],
+}
+# seconds a launch may take: five times its first passing run on an MI355X, at least 120.  Those runs took 4.9, 6.6, 10.6, 6.4 and
+# 9.0 s on 2, 3, 4, 5 and 8 ranks and 4.8 s for the selftest (notes/README.md has the cases' figures): 120 everywhere
+LAUNCH_TIMEOUT = {2: 120, 3: 120, 4: 120, 5: 120, 8: 120, "selftest": 120}
+FAULT = []  # the note a launch leaves that timed out, ended by a signal or reported a GPU fault: nothing more is started after it
+_results = {}
+ILLEGAL = "an illegal memory access was encountered"
+
+
+@pytest.fixture(autouse=True)
+def _nothing_after_a_fault():
+    if FAULT:
+        pytest.fail("not started: an earlier launch faulted or hung (%s)" % FAULT[0])
+
+
+def _launch(key, world, port, args):
+    """One torch.distributed.run of the worker (at most eight ranks, one launch at a time); the parsed RESULT, cached."""
+    if FAULT:
+        pytest.fail("not started: an earlier launch faulted or hung (%s)" % FAULT[0])
+    if key in _results:
+        kind, val = _results[key]
+        if kind == "error":
+            pytest.fail("the launch of %s failed: %s" % (key, val))
+        return val
+    assert world <= 8
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
+    for name in ("ABG_FORCE_DIST", "ABG_DIST_ROUTE_MIN", "ABG_SLICE_FILTER"):
+        env.pop(name, None)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
+           "--master-port", str(port), WORKER] + args
+    t0 = time.time()
+    try:
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=LAUNCH_TIMEOUT[key])
+    except subprocess.TimeoutExpired as e:
+        FAULT.append("launch %s: no end within %d s" % (key, LAUNCH_TIMEOUT[key]))
+        _results[key] = ("error", FAULT[-1])
+        pytest.fail(FAULT[-1] + ": " + ((e.stderr or b"").decode(errors="replace")[-2000:]))
+    wall = time.time() - t0
+    text = r.stdout.decode(errors="replace") + r.stderr.decode(errors="replace")
+    # (the launcher reports a rank that a signal ended as "exitcode  : -11")
+    if r.returncode < 0 or r.returncode in (134, 139, 124, 137) or ILLEGAL in text or re.search(r"exitcode\s*:\s*(-\d+|134|139|124|137)\b", text):
+        FAULT.append("launch %s: status %d" % (key, r.returncode))
+    if r.returncode != 0:
+        _results[key] = ("error", "status %d: %s" % (r.returncode, text[-3000:]))
+        pytest.fail(_results[key][1])
+    out = result_of(r)
+    print("launch %s: %.1f s" % (key, wall))
+    for spec, v in out.items():  # (the figures notes/README.md records)
+        if isinstance(v, dict):
+            print("  %s: %s s, all_to_all_v %d," % (spec, v["seconds"], v["comm_calls"]["all_to_all_v"]), {n: v["stats"][n] for n in (
+                "commit_rounds", "walk_rounds", "insert_rounds", "tiled_ops", "tiled_pending", "tile_overflows", "counter_bytes_held")})
+    _results[key] = ("ok", out)
+    return out
+
+
+@pytest.fixture(scope="module")
+def hard_cases():
+    """world -> {SPEC: what the worker collected for it}; the launch of a world size is made when its first test asks."""
+    return lambda world: _launch(world, world, 29740 + world, ["cases"] + LAUNCHES[world])
+
+
+def _parse(spec):
+    head, _, tail = spec.partition(":")
+    name, _, arg = head.partition("+")
+    env = dict(item.split("=", 1) for item in tail.split(",") if item)
+    if "route" in env:
+        env["ABG_DIST_ROUTE_MIN"] = env.pop("route")
+    return name, arg, env
+
+
+def _counters_of(name, arg):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dist_cases
+    if name == "golden":
+        return json.load(open(os.path.join(ROOT, "tests", "golden", arg + ".json")))["counters"]
+    if name in dist_cases.SYNTHETIC:
+        return dist_cases.SYNTHETIC[name][2]
+    return {"saturate": 4096, "saturate_tiled": 1 << 22, "kept": 1 << 20, "sliced_checkpoint": 1 << 19}[name]
+
+
+@pytest.mark.parametrize("world,spec", [(w, s) for w in sorted(LAUNCHES) for s in LAUNCHES[w]], ids=lambda v: "w%d" % v if isinstance(v, int) else v)
+def test_hard_cases_of_the_partitioned_path_with_the_real_kernels(world, spec, hard_cases):
+    """The assertions of the CPU twins in tests/test_dist_partition.py (same bytes, same knobs: tests/dist_cases.py), on
+    ranks that exchange data between real kernels: the 64-lane votes of the partitioned commit where their answer decides a
+    second pass, atomics between workgroups, LDS tiles, kernels behind staged collectives; from four ranks on the routed
+    exchange over uneven owner ranges.  Besides the verdicts, each case must have taken its path."""
+    out = hard_cases(world)[spec]
+    name, arg, env = _parse(spec)
+    keys = ("filtered_popcount", "fasta", "readlog", "trace", "counters") if name == "golden" else \
+        ("counting_filter",) if name.startswith("saturate") else ("counting_filter", "results", "contigs", "visited", "assembly_counters")
+    for key in keys + ("ranks_agree",):
+        assert out[key] is True, (key, out)
+    st, calls = out["stats"], out["comm_calls"]
+    assert calls["all_reduce"] > 0, calls
+    route = env.get("ABG_DIST_ROUTE_MIN")
+    if "ABG_ROUTE_CAP" in env:
+        # Engine::insert_tiles_routed learns that a sender's room ran out from the all-reduce of the counts, BEFORE the first
+        # exchange: a batch that falls back never calls all_to_all_v, and with a room this small every batch does (the CPU
+        # twin: all_to_all_v == 0, 14 fall-backs).  That the routed pack ran is shown by the fall-backs themselves -- only it
+        # reads ABG_ROUTE_CAP -- and by nothing having gone through the tiles.
+        assert st["tile_overflows"] > 0 and st["tiled_ops"] == 0, st
+    elif world >= 4 or route == "2":
+        assert calls["all_to_all_v"] > 0, calls
+    if route == "0":
+        assert calls["all_to_all_v"] == 0, calls
+    if name == "bigbatch":
+        assert st["commit_rounds"] > st["walk_rounds"], st
+        assert out["n_contigs"] > 20
+    if name == "tiny_filter":
+        assert st["insert_rounds"] > 20, st
+    if name.startswith("saturate"):
+        assert out["saturated"] == 255, out
+    if name == "saturate_tiled":
+        assert st["tiled_ops"] > 0 and st["tiled_pending"] > 254, st
+    if "ABG_TILE_CAP" in env or "ABG_ROUTE_CAP" in env:
+        assert st["tile_overflows"] > 0, st
+    if env.get("ABG_TILED") == "0":
+        assert st["tiled_ops"] == 0, st
+    if env.get("ABG_SLICE_FILTER") == "1":
+        assert 0 < st["counter_bytes_held"] <= _counters_of(name, arg) // world + 128, st
+    if name in ("kept", "oracle"):
+        assert out["n_contigs"] > 10
+
+
+def test_communicator_selftest_on_device_buffers_world4():
+    """abyss_amd.dist.selftest over StagedTorchComm with the buffers in device memory (torch tensors, moved through
+    abg_dev_copy): all 10 checks on every rank.  The CPU twin only ever used host memory."""
+    out = _launch("selftest", 4, 29750, ["selftest"])
+    assert len(out["ranks"]) == 4
+    for r in out["ranks"]:
+        assert r["ok"] and r["checks"] == 10 and not r["failed"], r
 
 
 def _gpus():
