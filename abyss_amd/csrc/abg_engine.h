@@ -2357,10 +2357,66 @@ struct GraphState {
 	uint32_t stop;     // 0 finished, 1 node buffer full, 2 table full
 	uint32_t pad_;
 };
+// Spaced-seed build only: where the vertex's k-mer holds a non-ACGT character (2-bit groups like the
+// k-mer's: 1 = not ACGT).  A START k-mer may have such characters beneath the seed's '0's, and the
+// reference keeps them in the k-mers of the vertices it reaches from there (LightweightKmer::shift
+// moves characters): one step on, a character that sat under the first '0' sits under a '1'.  ntHash's
+// seed for it is 0 (nthash.hpp seedTab), so it adds nothing to either strand hash, and
+// LightweightKmer::isCanonical compares it as the letter it is.  The packed k-mer holds some base in
+// its place; its terms are taken out again here.
+template <int NW, bool M = MASKED_BUILD<NW>> struct GNode { Vtx<NW> v; };
+template <int NW> struct GNode<NW, true> { Vtx<NW> v; Kmer<NW> n; };
+template <int NW>
+ABG_HD bool gnode_clean(const GNode<NW>& g)
+{
+	if constexpr (MASKED_BUILD<NW>) {
+		uint64_t a = 0;
+#pragma unroll
+		for (int j = 0; j < KW<NW>; j++) a |= g.n.w[j];
+		return a == 0;
+	} else { (void)g; return true; }
+}
+// canonical hash and table key of a search vertex (vtx_hash / vtx_key with the above)
+template <int NW>
+ABG_HD void gnode_hash_key(const Params& p, const GNode<NW>& g, uint64_t& h, VKey& key)
+{
+	if (gnode_clean(g)) { h = vtx_hash(p, g.v); key = vtx_key(p, g.v); return; }
+	if constexpr (MASKED_BUILD<NW>) {
+		const unsigned k = p.k;
+		uint64_t fs, rs;
+		strand_hashes(g.v, fs, rs);
+		for (unsigned i = 0; i < k; i++) {
+			if (!kmer_get(g.n, i) || !pos_cared(p, i)) continue; // (under a '0' its terms are XORed out already)
+			const unsigned x = kmer_get(g.v.s, i);
+			fs ^= srol_n(seed_of(x), k - 1 - i);
+			rs ^= srol_n(seed_of(3u - x), i);
+		}
+		h = rs < fs ? rs : fs;
+		// isCanonical over the characters: 'A' < 'C' < 'G' < 'N' < 'T', and 'N' is its own complement
+		bool canon = true;
+		for (unsigned i = 0; i < k / 2; i++) {
+			const unsigned c1 = kmer_get(g.n, i) ? 5u : 2u * kmer_get(g.v.s, i);
+			const unsigned c2 = kmer_get(g.n, k - 1 - i) ? 5u : 2u * (3u - kmer_get(g.v.s, k - 1 - i));
+			if (c1 != c2) { canon = c1 < c2; break; }
+		}
+		VKey id;
+		id.fh = canon ? fs : rs;
+		id.rh = canon ? rs : fs;
+		key = wt_key(id);
+	}
+}
+template <int NW>
+ABG_HD GNode<NW> gnode_successor(const Params& p, const GNode<NW>& u, unsigned b)
+{
+	GNode<NW> w;
+	w.v = neighbour_vertex(p, u.v, SENSE, b);
+	if constexpr (MASKED_BUILD<NW>) { w.n = u.n; kmer_shift(w.n, p.k, SENSE, 0u); }
+	return w;
+}
 template <int NW>
 struct FGraphBfs {
-	Params p; const uint8_t* cnt; Batch starts; uint64_t nstarts; WalkTab tab; uint64_t tab_limit;
-	Vtx<NW>* nodes; uint64_t node_cap; uint8_t* ev; uint8_t* start_used; GraphState* st;
+	Params p; const uint8_t* cnt; Batch starts; Batch marks; uint64_t nstarts; WalkTab tab; uint64_t tab_limit;
+	GNode<NW>* nodes; uint64_t node_cap; uint8_t* ev; uint8_t* start_used; GraphState* st;
 	ABG_HDN void operator()(uint64_t, uint32_t) const
 	{
 		GraphState s = *st;
@@ -2369,14 +2425,15 @@ struct FGraphBfs {
 			while (s.head < s.count && !s.stop) {
 				if (s.count + 4 > node_cap) { s.stop = 1; break; }
 				if (s.tab_used + 4 > tab_limit) { s.stop = 2; break; }
-				const Vtx<NW> u = nodes[s.head];
+				const GNode<NW> u = nodes[s.head];
 				unsigned e = 0;
 				for (unsigned b = 0; b < 4; b++) { // out_edge_iterator, RollingBloomDBG.h:299-330
-					Vtx<NW> w = neighbour_vertex(p, u, SENSE, b);
-					if (!solid_contains(p, cnt, vtx_hash(p, w))) continue;
+					const GNode<NW> w = gnode_successor(p, u, b);
+					uint64_t h; VKey key;
+					gnode_hash_key(p, w, h, key);
+					if (!solid_contains(p, cnt, h)) continue;
 					e |= 1u << b;
 					s.edges++;
-					const VKey key = vtx_key(p, w);
 					if (wt_find(tab, key, 0) != WT_EMPTY) continue;
 					wt_insert(tab, key, 0, 0);
 					s.tab_used++;
@@ -2388,10 +2445,12 @@ struct FGraphBfs {
 			if (s.stop || s.s_next >= nstarts) break;
 			if (s.count + 1 > node_cap) { s.stop = 1; break; }
 			if (s.tab_used + 1 > tab_limit) { s.stop = 2; break; }
-			Vtx<NW> v;
-			v.s = batch_kmer<NW>(starts, s.s_next, 0, p.k);
-			vtx_rehash(p, v);
-			const VKey key = vtx_key(p, v);
+			GNode<NW> v;
+			v.v.s = batch_kmer<NW>(starts, s.s_next, 0, p.k);
+			vtx_rehash(p, v.v);
+			if constexpr (MASKED_BUILD<NW>) v.n = batch_kmer<NW>(marks, s.s_next, 0, p.k);
+			uint64_t h; VKey key;
+			gnode_hash_key(p, v, h, key);
 			if (wt_find(tab, key, 0) != WT_EMPTY) {
 				start_used[s.s_next] = 0; // not white: nothing printed, nothing queued (:117-131)
 			} else {
@@ -3445,14 +3504,16 @@ class Engine {
 	// ---- -g: the breadth-first searches from `starts` (sequences of k bases) in order; ev gets one
 	// byte per vertex in discovery order, used one flag per start (see FGraphBfs).  The set of seen
 	// vertices carries over between calls (the reference's colour map spans all input files).
-	void graph_bfs(const Batch& starts, std::vector<uint8_t>& ev, std::vector<uint8_t>& used, uint64_t* edges)
+	// Under a spaced seed `marks` has a sequence per start as well: C where the start's character is not
+	// one of ACGT, A elsewhere (see GNode).
+	void graph_bfs(const Batch& starts, const Batch& marks, std::vector<uint8_t>& ev, std::vector<uint8_t>& used, uint64_t* edges)
 	{
 		ev.clear(); used.assign(starts.n, 0);
 		*edges = 0;
 		if (!starts.n) return;
 		need_whole_filter("-g");
 		gather_counters();
-		dispatch_nw([&](auto nw) { graph_bfs_nw<decltype(nw)::value>(starts, ev, used, edges); });
+		dispatch_nw([&](auto nw) { graph_bfs_nw<decltype(nw)::value>(starts, marks, ev, used, edges); });
 	}
 
 	// ---- PASS 1 on a device-resident packed batch (ops are inserted in batch order).
@@ -4008,11 +4069,11 @@ class Engine {
 		}
 	}
 	template <int NW>
-	void graph_bfs_nw(const Batch& starts, std::vector<uint8_t>& ev, std::vector<uint8_t>& used, uint64_t* edges)
+	void graph_bfs_nw(const Batch& starts, const Batch& marks, std::vector<uint8_t>& ev, std::vector<uint8_t>& used, uint64_t* edges)
 	{
 		if (!gtab_.hmin) { alloc_tab(gtab_, 16); gtab_used_ = 0; }
 		uint64_t node_cap = 1ull << 16;
-		Vtx<NW>* nodes = (Vtx<NW>*)be_.alloc(node_cap * sizeof(Vtx<NW>));
+		GNode<NW>* nodes = (GNode<NW>*)be_.alloc(node_cap * sizeof(GNode<NW>));
 		uint8_t* ev_d = (uint8_t*)be_.alloc(node_cap);
 		uint8_t* used_d = (uint8_t*)be_.alloc(starts.n);
 		GraphState* st_d = (GraphState*)be_.alloc(sizeof(GraphState));
@@ -4021,11 +4082,11 @@ class Engine {
 		st.tab_used = gtab_used_;
 		be_.h2d(st_d, &st, sizeof st);
 		for (;;) {
-			FGraphBfs<NW> f{ p_, cnt_, starts, starts.n, gtab_, (gtab_.mask + 1) / 2, nodes, node_cap, ev_d, used_d, st_d };
+			FGraphBfs<NW> f{ p_, cnt_, starts, marks, starts.n, gtab_, (gtab_.mask + 1) / 2, nodes, node_cap, ev_d, used_d, st_d };
 			be_.launch(1, f, "graph_bfs");
 			be_.d2h(&st, st_d, sizeof st);
 			if (st.stop == 1) {
-				nodes = (Vtx<NW>*)regrow(nodes, node_cap * sizeof(Vtx<NW>), 2 * node_cap * sizeof(Vtx<NW>));
+				nodes = (GNode<NW>*)regrow(nodes, node_cap * sizeof(GNode<NW>), 2 * node_cap * sizeof(GNode<NW>));
 				ev_d = (uint8_t*)regrow(ev_d, node_cap, 2 * node_cap);
 				node_cap *= 2;
 			} else if (st.stop == 2) {

@@ -365,6 +365,15 @@ class Session {
 		return ABG_OK;
 	}
 	uint64_t kept_reads() { drain(); return keep_on_ ? keep_.n_reads : 0; }
+	// abg_reset: the state right after abg_create -- the engine's, and no reads kept nor keeping switched on
+	void reset()
+	{
+		drain();
+		keep_drop(false);
+		keep_on_ = false;
+		keep_.hint_words = 0;
+		eng->reset();
+	}
 	int assemble_kept(uint8_t* results, abg_contig_cb cb, void* user)
 	{
 		drain();
@@ -615,8 +624,10 @@ class Session {
 	// the GraphViz lines between "digraph g {" and "}", delivered in chunks.  trimSeq and the
 	// searches run on the device (FTrimRun, FGraphBfs); the host turns the recorded visiting order
 	// back into k-mer strings: a successor's k-mer is its parent's shifted by one base.
-	// (Under a spaced seed, a non-ACGT character beneath a '0' of a START k-mer would be printed by
-	// the reference as it stands in the read; here it comes out as 'N' -- the one known deviation.)
+	// Under a spaced seed a START k-mer may hold non-ACGT characters beneath the seed's '0's; where they are
+	// goes to the device beside the packed k-mers (`marks`), since the vertices reached from such a start
+	// keep them (GNode, abg_engine.h).  (The reference would print such a character as it stands in the
+	// read; here it comes out as 'N' whatever it was -- the one known deviation.)
 	int output_graph_seqs(const char* seqs, const uint64_t* off, uint64_t n, abg_text_cb cb, void* user,
 	    uint64_t* nodes_out, uint64_t* edges_out)
 	{
@@ -650,7 +661,8 @@ class Session {
 		}
 		// per read: the first longest run over its segments; start vertices = its first k-mer and the
 		// reverse complement of its last k-mer (:1217-1226)
-		HostBatch starts;
+		HostBatch starts, marks; // (marks, spaced seed only: where a start k-mer is not ACGT -- beneath a '0')
+		const bool masked = !cfg.spaced_seed.empty();
 		std::vector<std::string> start_kmers;
 		auto fold = [](char c) { c = (char)toupper((unsigned char)c); return (c == 'A' || c == 'C' || c == 'G' || c == 'T') ? c : 'N'; };
 		auto comp = [](char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : 'N'; };
@@ -668,6 +680,12 @@ class Session {
 				}
 				starts.add_ascii(first.data(), k, k);
 				starts.add_ascii(rc.data(), k, k);
+				if (masked)
+					for (const std::string* sk : { &first, &rc }) {
+						std::string m(k, 'A');
+						for (uint32_t j = 0; j < k; j++) if ((*sk)[j] == 'N') m[j] = 'C';
+						marks.add_ascii(m.data(), k, k);
+					}
 				start_kmers.push_back(first);
 				start_kmers.push_back(rc);
 			}
@@ -676,8 +694,10 @@ class Session {
 		std::vector<uint8_t> ev, used;
 		uint64_t edges = 0;
 		if (starts.n()) {
-			DevBatch d = upload(starts);
-			eng->graph_bfs(d.b, ev, used, &edges);
+			DevBatch d = upload(starts), dm{};
+			if (masked) dm = upload(marks);
+			eng->graph_bfs(d.b, dm.b, ev, used, &edges);
+			if (masked) release(dm);
 			release(d);
 		}
 		// replay

@@ -901,7 +901,8 @@ int abg_reset(abg_ctx* ctx)
 {
 	if (!ctx) return ABG_EINVAL;
 	return guarded(ctx, [&]() -> int {
-		ctx->s.eng->reset();
+		(void)hipSetDevice(ctx->s.be.device);
+		ctx->s.reset();
 		ctx->s.be.sync();
 		return ABG_OK;
 	});

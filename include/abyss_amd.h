@@ -127,7 +127,8 @@ const char* abg_last_error(const abg_ctx* ctx); /* ctx may be NULL: error of the
 
 /* Empty filters, zero counters, empty contigEndKmers: the state right after abg_create, keeping the
  * device memory (what destroying and re-creating the context would do, minus ~26 GB of hipFree /
- * hipMalloc for a 2G filter).  Tuning and parameters are unchanged. */
+ * hipMalloc for a 2G filter).  Reads kept for abg_assemble_kept are dropped and keeping is switched
+ * off (abg_keep_reads); the vertices -g has seen are forgotten.  Tuning and parameters are unchanged. */
 int abg_reset(abg_ctx* ctx);
 
 /* bloom.size() / sizeInBytes(): number of uint8 counters == number of visited bits */

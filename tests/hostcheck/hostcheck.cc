@@ -210,7 +210,7 @@ void* hc_create_cascade(unsigned k, unsigned nh, unsigned levels, uint64_t level
 }
 uint8_t* hc_cascade_level(void* h, unsigned l) { return S(h)->eng->cascade_level_dev(l); }
 void hc_destroy(void* h) { delete (Sess*)h; }
-void hc_reset(void* h) { S(h)->eng->reset(); }
+void hc_reset(void* h) { S(h)->reset(); }
 uint64_t hc_size(void* h) { return S(h)->eng->size(); }
 uint8_t* hc_counters(void* h)
 {

@@ -405,8 +405,9 @@ def test_chunked_calls_equal_single_call():
 @pytest.mark.parametrize("name", ["k32", "k40_mixed", "k48_K16", "k25_h3_kc3_t40"])
 def test_graphviz_dump_device_logic_matches_reference(name):
     """-g: trimSeq + the breadth-first searches (FTrimRun, FGraphBfs) and the host's replay against the
-    file the unmodified reference wrote (SHA-256, size, visitor counters); the vertex table and the node
-    buffer start small, so both grow on the way."""
+    file the unmodified reference wrote (SHA-256, size, visitor counters).  None of these graphs reaches
+    the first size of the node buffer (2^16 vertices) or of the vertex table (2^15 entries): growing them
+    is tests/test_graph_hostcheck.py's business."""
     import hashlib
     g = GoldenCase(name)
     kw = g.kwargs()
