@@ -64,6 +64,8 @@ def symbols():
         "abg_rr_contains_seqs", "abg_rr_popcount", "abg_rr_export", "abg_rr_sync", "abg_rr_profile", "abg_rr_profile_get",
         "abg_kn_create", "abg_kn_destroy", "abg_kn_last_error", "abg_kn_import", "abg_kn_export", "abg_kn_insert_seqs",
         "abg_kn_contains_seqs", "abg_kn_popcount", "abg_kn_hash_seq", "abg_kn_sync", "abg_kn_profile", "abg_kn_profile_get",
+        "abg_fm_create", "abg_fm_destroy", "abg_fm_last_error", "abg_fm_build", "abg_fm_size", "abg_fm_export", "abg_fm_map_seqs",
+        "abg_fm_sync", "abg_fm_tune", "abg_fm_profile", "abg_fm_profile_get",
     ]
 
 
@@ -155,5 +157,18 @@ def load(path: str | None = None):
     lib.abg_kn_sync.argtypes = [vp]
     lib.abg_kn_profile.argtypes = [vp, C.c_int]
     lib.abg_kn_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
+    lib.abg_fm_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.abg_fm_destroy.argtypes = [vp]
+    lib.abg_fm_destroy.restype = None
+    lib.abg_fm_last_error.argtypes = [vp]
+    lib.abg_fm_last_error.restype = C.c_char_p
+    lib.abg_fm_build.argtypes = [vp, vp, C.c_uint64]
+    lib.abg_fm_size.argtypes = [vp, u64p]
+    lib.abg_fm_export.argtypes = [vp, vp, vp]
+    lib.abg_fm_map_seqs.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]
+    lib.abg_fm_sync.argtypes = [vp]
+    lib.abg_fm_tune.argtypes = [vp, C.c_uint32]
+    lib.abg_fm_profile.argtypes = [vp, C.c_int]
+    lib.abg_fm_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
     _lib = lib
     return lib

@@ -606,3 +606,76 @@ class KonnectorBloom:
         ms, n = C.c_double(), C.c_uint64()
         self._lib.abg_kn_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
         return ms.value, n.value
+
+
+FM_HIT = np.dtype([("l", "<u4"), ("u", "<u4"), ("qstart", "<u4"), ("qend", "<u4"), ("num", "<u4"), ("pos", "<u4")])
+
+
+class FMIndex:
+    """The FM-index of abyss-map and abyss-index on one GPU: the whole target file as text, alphabet -ACGT (FMIndex/FMIndex.h,
+    Map/map.cc; include/abyss_amd.h abg_fm_*).  The occurrence table and the full suffix array stay in device memory."""
+
+    def __init__(self, device: int = 0):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        rc = self._lib.abg_fm_create(device, C.byref(self._h))
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_fm_last_error(None)
+            self._h = None
+            raise AbyssAmdError("abg_fm_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.abg_fm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_fm_last_error(self._h)
+            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+
+    def build(self, text: bytes) -> None:
+        """FMIndex::assign over the raw bytes of the target file."""
+        keep = C.c_char_p(text)
+        self._check(self._lib.abg_fm_build(self._h, C.cast(keep, C.c_void_p), len(text)), "abg_fm_build")
+
+    def size(self) -> int:
+        n = C.c_uint64()
+        self._check(self._lib.abg_fm_size(self._h, C.byref(n)), "abg_fm_size")
+        return n.value
+
+    def export(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(SA, BWT): size() + 1 entries each, the BWT as codes 0..4 with 255 for the sentinel."""
+        m = self.size() + 1
+        sa, bwt = np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.uint8)
+        self._check(self._lib.abg_fm_export(self._h, sa.ctypes.data, bwt.ctypes.data), "abg_fm_export")
+        return sa, bwt
+
+    def map(self, buf: bytes, offsets: np.ndarray, min_len: int, ss: bool = False, rc: bool = True) -> np.ndarray:
+        """findMatch of every sequence: an array of shape (n, 2) of FM_HIT, [:, 0] the forward strand, [:, 1] the reverse complement."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(off) - 1
+        out = np.zeros((n, 2), dtype=FM_HIT)
+        keep = C.c_char_p(buf)
+        flags = (0 if rc else 1) | (2 if ss else 0)
+        self._check(self._lib.abg_fm_map_seqs(self._h, C.cast(keep, C.c_void_p), off.ctypes.data, n, min_len, flags,
+                                              out.ctypes.data if n else None), "abg_fm_map_seqs")
+        return out
+
+    def tune(self, waves_per_cu: int) -> None:
+        """Search lanes = CUs x waves_per_cu x 64 (1..32; 0 restores the default)."""
+        self._check(self._lib.abg_fm_tune(self._h, waves_per_cu), "abg_fm_tune")
+
+    def profile(self, on: bool = True) -> None:
+        self._lib.abg_fm_profile(self._h, int(on))
+
+    def profile_get(self, name: str) -> Tuple[float, int]:
+        ms, n = C.c_double(), C.c_uint64()
+        self._lib.abg_fm_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
+        return ms.value, n.value

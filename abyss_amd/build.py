@@ -55,6 +55,7 @@ UNITS = {
     "abg_kernels": ["abg_kernels.hip", "abg_core.h", "abg_engine.h", "abg_walk.h", "abg_host.h", "abg_overlap.h"],
     "abg_rr": ["abg_rr.hip", "abg_rr.h", "abg_core.h"],
     "abg_kn": ["abg_kn.hip", "abg_kn.h", "abg_core.h"],
+    "abg_fm": ["abg_fm.hip", "abg_fm.h", "abg_core.h"],
 }
 
 
@@ -100,6 +101,10 @@ def build_cli(force: bool = False) -> str:
         _run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-o",
               os.path.join(BIN_DIR, "abyss-rresolver-short"), os.path.join(CSRC, "host", "rresolver_main.cc"),
               "-L" + os.path.dirname(LIB), "-labyss_amd", "-Wl,-rpath,$ORIGIN/../lib", "-lpthread"])
+        for name, main in (("abyss-map", "map_main.cc"), ("abyss-index", "index_main.cc")):
+            _run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-o",
+                  os.path.join(BIN_DIR, name), os.path.join(CSRC, "host", main),
+                  "-L" + os.path.dirname(LIB), "-labyss_amd", "-Wl,-rpath,$ORIGIN/../lib", "-lpthread"])
     return out
 
 
@@ -117,6 +122,7 @@ READER_CHECK = os.path.join(ROOT, "tests", "hostcheck", "reader_check")
 ADJLIST_CHECK = os.path.join(ROOT, "tests", "hostcheck", "adjlist_check")
 RRESOLVER_CHECK = os.path.join(ROOT, "tests", "hostcheck", "rresolver_check")
 KN_CHECK = os.path.join(ROOT, "tests", "hostcheck", "kn_check")
+FM_CHECK = os.path.join(ROOT, "tests", "hostcheck", "fm_check")
 
 
 def build_hostcheck(force: bool = False) -> str:
@@ -141,6 +147,11 @@ def build_hostcheck(force: bool = False) -> str:
         [os.path.join(CSRC, "host", f) for f in ("bloom_core.h", "fasta_reader.h")]
     if force or _newer(KN_CHECK, kdeps):
         _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", KN_CHECK, ksrc, "-lpthread"])
+    fsrc = os.path.join(ROOT, "tests", "hostcheck", "fm_check.cc")
+    fdeps = [fsrc] + [os.path.join(CSRC, f) for f in ("abg_fm.h", "abg_core.h")] + \
+        [os.path.join(CSRC, "host", f) for f in ("map_core.h", "fasta_reader.h")]
+    if force or _newer(FM_CHECK, fdeps):
+        _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", FM_CHECK, fsrc, "-lpthread"])
     return HOSTCHECK
 
 

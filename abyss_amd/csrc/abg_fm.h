@@ -1,0 +1,178 @@
+// abg_fm.h -- the FM-index of abyss-map and abyss-index (bin/abyss-pe:620-645, 710-735): occurrence table, backward
+// search and locate.
+//
+// Reference behaviour restated here (ABySS 2.3.10, paths relative to the repo):
+//   Map/map.cc:501-520         the text is the whole FASTA file, header lines included, upper-cased
+//   FMIndex/FMIndex.h:186-187  alphabet "-ACGT" -> codes 0..4; every other byte is the sentinel, then replaced by 0
+//   FMIndex/FMIndex.h:180-215  SA[0] = n, SA[1..n] the suffixes in lexicographic order (a prefix sorts first),
+//                              BWT[i] = text[SA[i] - 1], the sentinel where SA[i] == 0
+//   FMIndex/FMIndex.h:570-578  cf[0] = 1, cf[c + 1] = cf[c] + count(c)
+//   FMIndex/FMIndex.h:303-313  update(i, c) = cf[c] + rank(c, i)
+//   FMIndex/FMIndex.h:400-447  findSuffix / findSubstring, memo and all (see fm_find)
+//   FMIndex/FMIndex.h:449-469  a query character outside the alphabet stops a search; case is not folded here (the
+//                              reader folds it)
+//   Map/map.cc:325-341         the reverse complement is searched after the forward strand, with k = its span
+//
+// The layout is this project's own: the BWT in 64-byte blocks of 128 symbols, each four running counts (A C G T before
+// the block) and three bit planes of the 3-bit codes, so one rank reads one block: 0.5 bytes a symbol.  Positions are
+// 32-bit: a text of 2^32 - 1 bytes or more is refused by abg_fm_build.
+//
+// Like abg_core.h everything is ABG_HD: the kernels of abg_fm.hip are thin wrappers, and tests/hostcheck/fm_check.cc
+// runs the same code serially for the CPU suite.  The product runs it on the GPU only.
+#pragma once
+#include "abg_core.h"
+
+namespace abg {
+
+constexpr uint32_t FM_BLOCK = 128;        // symbols a table block
+constexpr unsigned FM_SENT = 7;           // the sentinel's code in the table's bit planes
+constexpr unsigned FM_STOP = 255;         // a query character outside the alphabet
+constexpr uint32_t FM_NOPOS = 0xFFFFFFFFu;
+constexpr uint32_t FM_WAVES_PER_CU = 8;  // search lanes = CUs x this x 64 unless abg_fm_tune says otherwise (notes/fm_map.md)
+constexpr uint32_t FM_FLAG_NORC = 1, FM_FLAG_SS = 2; // abg_fm_map_seqs flags (include/abyss_amd.h)
+
+struct alignas(64) FMBlock {
+	uint32_t cnt[4];              // A C G T in the blocks before this one
+	uint32_t p0[4], p1[4], p2[4]; // bit j of the code of symbol i: word i / 32, bit i % 32
+};
+
+struct FMView {
+	const FMBlock* occ; // m / 128 + 1 blocks: rank(c, m) reads the block after the last symbol
+	uint32_t cf[5];
+	uint32_t m;         // n + 1: the BWT's length
+	uint32_t sent;      // where the sentinel stands in the BWT
+};
+
+struct FMHit { uint32_t l, u, qstart, qend, num, pos; }; // abg_fm_hit of include/abyss_amd.h
+
+ABG_HD unsigned fm_popc(uint32_t x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	return (unsigned)__popc(x);
+#else
+	return (unsigned)__builtin_popcount(x);
+#endif
+}
+
+// a byte of the target file -> 0..4 (::toupper first; whatever is not A C G T ends as 0, '-' included)
+ABG_HD unsigned fm_text_code(unsigned c)
+{
+	if (c >= 'a' && c <= 'z') c -= 32;
+	return c == 'A' ? 1u : c == 'C' ? 2u : c == 'G' ? 3u : c == 'T' ? 4u : 0u;
+}
+// a query character -> 0..4 or FM_STOP (Translate)
+ABG_HD unsigned fm_query_code(unsigned c)
+{
+	return c == 'A' ? 1u : c == 'C' ? 2u : c == 'G' ? 3u : c == 'T' ? 4u : c == '-' ? 0u : FM_STOP;
+}
+// the complement of a (folded) read character; whatever is not A C G T stays outside the alphabet
+ABG_HD unsigned fm_complement(unsigned c)
+{
+	return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : 'N';
+}
+
+// planes and symbol counts of block b of a BWT of m codes (0..4, FM_SENT); cnt is left to the caller's running sum
+ABG_HD void fm_fill_block(const uint8_t* __restrict__ bwt, uint32_t m, uint32_t b, FMBlock& out, uint32_t local[4])
+{
+	for (int w = 0; w < 4; w++) out.p0[w] = out.p1[w] = out.p2[w] = 0;
+	for (int c = 0; c < 4; c++) { out.cnt[c] = 0; local[c] = 0; }
+	const uint64_t base = (uint64_t)b * FM_BLOCK;
+	for (uint32_t i = 0; i < FM_BLOCK && base + i < m; i++) {
+		const unsigned c = bwt[base + i];
+		const uint32_t bit = 1u << (i & 31);
+		if (c & 1) out.p0[i >> 5] |= bit;
+		if (c & 2) out.p1[i >> 5] |= bit;
+		if (c & 4) out.p2[i >> 5] |= bit;
+		if (c >= 1 && c <= 4) local[c - 1]++;
+	}
+}
+
+// how many of the first r symbols of a block match: `one` the code 1..4, or 0 for "any of 1..4"
+ABG_HD uint32_t fm_inblock(const FMBlock& b, unsigned c, uint32_t r)
+{
+	uint32_t s = 0;
+	for (uint32_t w = 0; w < 4; w++) {
+		const uint32_t lo = 32 * w;
+		const uint32_t mask = r >= lo + 32 ? ~0u : r > lo ? (1u << (r - lo)) - 1 : 0u;
+		uint32_t hit;
+		if (c) hit = ((c & 1) ? b.p0[w] : ~b.p0[w]) & ((c & 2) ? b.p1[w] : ~b.p1[w]) & ((c & 4) ? b.p2[w] : ~b.p2[w]);
+		else hit = (b.p0[w] | b.p1[w] | b.p2[w]) & ~(b.p0[w] & b.p1[w] & b.p2[w]);
+		s += fm_popc(hit & mask);
+	}
+	return s;
+}
+
+// occurrences of code c in BWT[0, i), i <= m
+ABG_HD uint32_t fm_rank(const FMView& v, unsigned c, uint32_t i)
+{
+	const FMBlock b = v.occ[i / FM_BLOCK];
+	const uint32_t r = i % FM_BLOCK;
+	if (c) return b.cnt[c - 1] + fm_inblock(b, c, r);
+	// code 0: what is neither A C G T nor the sentinel
+	const uint32_t acgt = b.cnt[0] + b.cnt[1] + b.cnt[2] + b.cnt[3] + fm_inblock(b, 0, r);
+	return i - acgt - (v.sent < i ? 1u : 0u);
+}
+
+ABG_HD uint32_t fm_update(const FMView& v, uint32_t i, unsigned c) { return v.cf[c] + fm_rank(v, c, i); }
+
+// the symbol at BWT[i] (0..4, FM_SENT)
+ABG_HD unsigned fm_bwt_at(const FMView& v, uint32_t i)
+{
+	const FMBlock& b = v.occ[i / FM_BLOCK];
+	const uint32_t w = (i % FM_BLOCK) >> 5, s = i & 31;
+	return ((b.p0[w] >> s) & 1) | (((b.p1[w] >> s) & 1) << 1) | (((b.p2[w] >> s) & 1) << 2);
+}
+
+// FMIndex::findSubstring over the query codes q(0 .. L): the longest match at least k long and how often that length was
+// seen.  `memo` holds one interval per query position -- get(j, l, u), set(j, l, u), all (0, 0) on entry -- and is
+// indexed L - 1 - pos as the reference's.  Reproduced as written there:
+//   * best starts as the empty match (0, 0, 0, k - 1) with num 1; a match of equal span counts into it even while it
+//     is still that start value;
+//   * on a memo hit findSuffix leaves before its --it, so the match carries the extended interval with qstart = pos + 1;
+//   * the search returns as soon as the remaining prefix is shorter than the best span.
+template <class Q, class M>
+ABG_HD FMHit fm_find(const FMView& v, Q q, uint32_t L, uint32_t k, M& memo)
+{
+	FMHit best = { 0, 0, 0, k > 0 ? k - 1 : 0, 1, FM_NOPOS };
+	for (uint32_t end = L; end > 0; --end) {
+		if (end < best.qend - best.qstart) return best;
+		uint32_t l = 1, u = v.m, mi = L - end;
+		int64_t it = (int64_t)end - 1;
+		for (; it >= 0 && l < u; --it) {
+			const unsigned c = q((uint32_t)it);
+			if (c == FM_STOP) break;
+			const uint32_t l1 = fm_update(v, l, c), u1 = fm_update(v, u, c);
+			if (l1 >= u1) break;
+			l = l1; u = u1;
+			uint32_t ml, mu;
+			memo.get(mi, ml, mu);
+			if (ml == l && mu == u) break; // this vertex of the prefix DAWG has been visited
+			memo.set(mi++, l, u);
+		}
+		const uint32_t qstart = (uint32_t)(it + 1), span = end - qstart;
+		if (span > best.qend - best.qstart) best = FMHit{ l, u, qstart, end, 1, FM_NOPOS };
+		else if (span == best.qend - best.qstart) best.num++;
+	}
+	return best;
+}
+
+// findMatch of Map/map.cc for one read s(0 .. L) (raw characters, already case-folded by the reader): out[0] the forward
+// strand, out[1] the reverse complement (all zero with FM_FLAG_NORC); pos = SA[l] of a non-empty match.  memo.reset()
+// must make every entry (0, 0) again.
+template <class S, class M>
+ABG_HD void fm_map_read(const FMView& v, const uint32_t* __restrict__ sa, S s, uint32_t L, uint32_t k, uint32_t flags, M& memo, FMHit* out)
+{
+	FMHit f = fm_find(v, [&](uint32_t i) { return fm_query_code(s(i)); }, L, k, memo);
+	FMHit r = { 0, 0, 0, 0, 0, FM_NOPOS };
+	if (!(flags & FM_FLAG_NORC)) {
+		const uint32_t k2 = (flags & FM_FLAG_SS) ? k : f.qend - f.qstart;
+		memo.reset();
+		r = fm_find(v, [&](uint32_t i) { return fm_query_code(fm_complement(s(L - 1 - i))); }, L, k2, memo);
+	}
+	if (f.l < f.u) f.pos = sa[f.l];
+	if (r.l < r.u) r.pos = sa[r.l];
+	out[0] = f;
+	out[1] = r;
+}
+
+} // namespace abg

@@ -1,0 +1,503 @@
+// abg_fm.hip -- gfx950 kernels and C ABI of the FM-index of abyss-map / abyss-index (include/abyss_amd.h, abg_fm_*; logic in
+// abg_fm.h).
+//
+//   build   the suffix array by prefix doubling: the suffixes are keyed by their first 21 symbols (3 bits each), radix-sorted
+//           (rocPRIM through hipcub), ranked by group heads (a max-scan), and re-sorted by (rank[i], rank[i + h]) with h
+//           doubling until every rank is distinct.  k_fm_bwt then writes SA[0] = n, the BWT and the sentinel's place, and
+//           k_fm_occ_fill / k_fm_occ_hdr the 64-byte table blocks of abg_fm.h with their running counts (four scans).
+//   k_fm_map  a lane per read: the steps of a backward search depend on each other, and a read does both strands in turn
+//           (the reverse complement's k is the forward span).  Lanes take reads from a ticket, since step counts vary with
+//           the errors of a read.  The memo (one interval a query position) lives in global memory, interleaved by lane so
+//           that a wave's entries j share cache lines; it is sized by the call's longest read, and long reads get fewer lanes.
+// Bound: a search step is two dependent 64-byte gathers into the table (l and u); at 0.5 bytes a symbol a 37.5 Mbp table is
+// 19 MB and is served from the Infinity Cache.  Algorithmic bytes = 2 sectors x 64 B x steps.
+//
+// Built with the rest of the library: hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/abyss_amd.h"
+#include "abg_fm.h"
+
+static_assert(sizeof(abg_fm_hit) == sizeof(abg::FMHit), "abg_fm_hit and abg::FMHit are one layout");
+
+namespace {
+
+constexpr unsigned SYM0 = 21; // symbols in the first round's key: 21 x 3 bits
+
+__global__ void __launch_bounds__(256) k_fm_encode(uint8_t* __restrict__ t, uint32_t n)
+{
+	const uint32_t step = gridDim.x * blockDim.x;
+	for (uint64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) t[i] = (uint8_t)abg::fm_text_code(t[i]);
+}
+
+// key of suffix i: its first 21 codes + 1 (1..5), 0 past the end, so that a suffix that is a prefix of another sorts first
+__global__ void __launch_bounds__(256) k_fm_key_first(const uint8_t* __restrict__ t, uint32_t n, uint64_t* __restrict__ key, uint32_t* __restrict__ idx)
+{
+	const uint32_t step = gridDim.x * blockDim.x;
+	for (uint64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+		uint64_t k = 0;
+		for (unsigned j = 0; j < SYM0; j++) k = (k << 3) | (i + j < n ? (uint64_t)t[i + j] + 1 : 0);
+		key[i] = k;
+		idx[i] = (uint32_t)i;
+	}
+}
+
+// head[j] = j + 1 where a new group of equal keys starts, else 0; *groups counts the heads
+__global__ void __launch_bounds__(256) k_fm_heads(const uint64_t* __restrict__ key, uint32_t n, uint32_t* __restrict__ head, uint32_t* groups)
+{
+	const uint32_t step = gridDim.x * blockDim.x;
+	uint32_t mine = 0;
+	for (uint64_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += step) {
+		const bool h = j == 0 || key[j] != key[j - 1];
+		head[j] = h ? (uint32_t)j + 1 : 0;
+		mine += h;
+	}
+	for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o, 64);
+	if ((threadIdx.x & 63) == 0 && mine) atomicAdd(groups, mine);
+}
+
+__global__ void __launch_bounds__(256) k_fm_scatter(const uint32_t* __restrict__ idx, const uint32_t* __restrict__ r, uint32_t n, uint32_t* __restrict__ rank)
+{
+	const uint32_t step = gridDim.x * blockDim.x;
+	for (uint64_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += step) rank[idx[j]] = r[j];
+}
+
+// key of suffix i = idx[j]: (rank[i], rank[i + h]), 0 for a second half past the end
+__global__ void __launch_bounds__(256) k_fm_key_next(const uint32_t* __restrict__ idx, const uint32_t* __restrict__ rank, uint32_t n, uint32_t h, unsigned bits,
+    uint64_t* __restrict__ key)
+{
+	const uint32_t step = gridDim.x * blockDim.x;
+	for (uint64_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += step) {
+		const uint32_t i = idx[j];
+		const uint64_t second = (uint64_t)i + h < n ? rank[i + h] : 0;
+		key[j] = ((uint64_t)rank[i] << bits) | second;
+	}
+}
+
+// sa[0] = n, sa[j] = idx[j - 1]; bwt[j] = the code before that suffix, FM_SENT where it starts the text
+__global__ void __launch_bounds__(256) k_fm_bwt(const uint8_t* __restrict__ t, const uint32_t* __restrict__ idx, uint32_t n, uint32_t* __restrict__ sa,
+    uint8_t* __restrict__ bwt, uint32_t* sent)
+{
+	const uint32_t step = gridDim.x * blockDim.x;
+	for (uint64_t j = blockIdx.x * blockDim.x + threadIdx.x; j <= n; j += step) {
+		const uint32_t s = j == 0 ? n : idx[j - 1];
+		sa[j] = s;
+		bwt[j] = s == 0 ? (uint8_t)abg::FM_SENT : t[s - 1];
+		if (s == 0) *sent = (uint32_t)j;
+	}
+}
+
+// a thread per table block: its planes, and its symbol counts into local[c * nb + b]
+__global__ void __launch_bounds__(256) k_fm_occ_fill(const uint8_t* __restrict__ bwt, uint32_t m, uint32_t nb, abg::FMBlock* __restrict__ occ, uint32_t* __restrict__ local)
+{
+	const uint32_t step = gridDim.x * blockDim.x;
+	for (uint64_t b = blockIdx.x * blockDim.x + threadIdx.x; b < nb; b += step) {
+		abg::FMBlock blk;
+		uint32_t cnt[4];
+		abg::fm_fill_block(bwt, m, (uint32_t)b, blk, cnt);
+		occ[b] = blk;
+		for (int c = 0; c < 4; c++) local[(uint64_t)c * nb + b] = cnt[c];
+	}
+}
+
+// the running counts (exclusive sums of local) into the blocks; the last block's thread leaves the totals
+__global__ void __launch_bounds__(256) k_fm_occ_hdr(const uint32_t* __restrict__ local, const uint32_t* __restrict__ excl, uint32_t nb, abg::FMBlock* __restrict__ occ,
+    uint32_t* __restrict__ totals)
+{
+	const uint32_t step = gridDim.x * blockDim.x;
+	for (uint64_t b = blockIdx.x * blockDim.x + threadIdx.x; b < nb; b += step)
+		for (int c = 0; c < 4; c++) {
+			const uint32_t e = excl[(uint64_t)c * nb + b];
+			occ[b].cnt[c] = e;
+			if (b == nb - 1) totals[c] = e + local[(uint64_t)c * nb + b];
+		}
+}
+
+// the memo of one lane: entry j at base[j * lanes]; reset() clears what the last search wrote
+struct LaneMemo {
+	uint2* base;
+	uint32_t lanes, high;
+	__device__ void get(uint32_t j, uint32_t& l, uint32_t& u) const { const uint2 e = base[(uint64_t)j * lanes]; l = e.x; u = e.y; }
+	__device__ void set(uint32_t j, uint32_t l, uint32_t u) { base[(uint64_t)j * lanes] = make_uint2(l, u); if (j >= high) high = j + 1; }
+	__device__ void reset() { for (uint32_t j = 0; j < high; j++) base[(uint64_t)j * lanes] = make_uint2(0, 0); high = 0; }
+};
+
+// grid x 256 == lanes; memo holds lanes x (longest read) entries, all zero on entry and on exit
+__global__ void __launch_bounds__(256) k_fm_map(abg::FMView v, const uint32_t* __restrict__ sa, const unsigned char* __restrict__ seqs, const uint64_t* __restrict__ off,
+    uint64_t n, uint32_t k, uint32_t flags, uint2* __restrict__ memo, uint32_t lanes, unsigned long long* ticket, unsigned long long* steps, abg::FMHit* __restrict__ out)
+{
+	const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+	if (g >= lanes) return;
+	LaneMemo m{ memo + g, lanes, 0 };
+	unsigned long long mine = 0; // query characters taken: search steps, two table blocks each (profiling)
+	for (;;) {
+		const uint64_t i = atomicAdd(ticket, 1ull);
+		if (i >= n) break;
+		const uint64_t a = off[i];
+		const uint32_t L = (uint32_t)(off[i + 1] - a);
+		const unsigned char* s = seqs + a;
+		abg::fm_map_read(v, sa, [&](uint32_t j) { mine++; return (unsigned)s[j]; }, L, k, flags, m, out + 2 * i);
+		m.reset();
+	}
+	if (steps) { // (lanes is a multiple of 256: every wave is whole here) one add a wave
+		for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o, 64);
+		if ((threadIdx.x & 63) == 0 && mine) atomicAdd(steps, mine);
+	}
+}
+
+struct Prof { double ms = 0; uint64_t launches = 0; };
+
+} // namespace
+
+struct abg_fm {
+	int device = 0;
+	hipStream_t stream = nullptr;
+	uint64_t n = 0; // the text's length; 0: nothing built
+	abg::FMView view{};
+	abg::FMBlock* occ = nullptr;
+	uint32_t* sa = nullptr; // n + 1
+	uint8_t* bwt = nullptr; // n + 1 codes (0..4, FM_SENT)
+	void* qdev = nullptr; size_t qcap = 0;  // queries: sequences, offsets, hits
+	uint2* memo = nullptr; size_t memo_cap = 0; // entries
+	unsigned long long* ticket = nullptr; // [0] the ticket, [1] the steps of a profiled call
+	uint64_t steps = 0;
+	uint32_t cus = 256, waves = abg::FM_WAVES_PER_CU;
+	bool profiling = false;
+	std::map<std::string, Prof> prof;
+	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
+	std::string error;
+	void drop_index()
+	{
+		if (occ) (void)hipFree(occ);
+		if (sa) (void)hipFree(sa);
+		if (bwt) (void)hipFree(bwt);
+		occ = nullptr; sa = nullptr; bwt = nullptr; n = 0;
+	}
+	~abg_fm()
+	{
+		(void)hipSetDevice(device);
+		if (stream) (void)hipStreamSynchronize(stream);
+		for (auto& e : pending) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
+		drop_index();
+		if (qdev) (void)hipFree(qdev);
+		if (memo) (void)hipFree(memo);
+		if (ticket) (void)hipFree(ticket);
+		if (stream) (void)hipStreamDestroy(stream);
+	}
+};
+
+namespace {
+
+std::string g_fm_create_error;
+
+bool fm_ok(abg_fm* f, hipError_t e, const char* what)
+{
+	if (e == hipSuccess) return true;
+	(void)hipGetLastError();
+	f->error = std::string(what) + " failed: " + hipGetErrorString(e);
+	return false;
+}
+int fm_code_of(hipError_t e) { return e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL; }
+
+struct Timed { // brackets a piece of stream work with events when profiling
+	abg_fm* f; const char* name; hipEvent_t a = nullptr, b = nullptr;
+	Timed(abg_fm* f, const char* name) : f(f), name(name)
+	{
+		if (!f->profiling) return;
+		(void)hipEventCreate(&a); (void)hipEventCreate(&b);
+		(void)hipEventRecord(a, f->stream);
+	}
+	~Timed()
+	{
+		if (!a) return;
+		(void)hipEventRecord(b, f->stream);
+		f->pending.push_back({ name, { a, b } });
+	}
+};
+void prof_drain(abg_fm* f)
+{
+	for (auto& e : f->pending) {
+		float ms = 0;
+		(void)hipEventSynchronize(e.second.second);
+		if (hipEventElapsedTime(&ms, e.second.first, e.second.second) == hipSuccess) { f->prof[e.first].ms += ms; f->prof[e.first].launches++; }
+		(void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second);
+	}
+	f->pending.clear();
+}
+
+// device buffers of one build, freed when it ends
+struct Scratch {
+	std::vector<void*> ptrs;
+	hipError_t get(void** p, size_t bytes)
+	{
+		const hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+		if (e == hipSuccess) ptrs.push_back(*p);
+		return e;
+	}
+	~Scratch() { for (void* p : ptrs) (void)hipFree(p); }
+};
+
+struct MaxOp { __host__ __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; } };
+
+#define FM_TRY(expr, what) do { const hipError_t e_ = (expr); if (!fm_ok(f, e_, what)) return fm_code_of(e_); } while (0)
+
+int build_index(abg_fm* f, const uint8_t* text, uint64_t n64)
+{
+	const uint32_t n = (uint32_t)n64, m = n + 1, nb = m / abg::FM_BLOCK + 1;
+	hipStream_t st = f->stream;
+	Scratch sc;
+	uint8_t* t = nullptr;
+	uint64_t *key_a = nullptr, *key_b = nullptr;
+	uint32_t *idx_a = nullptr, *idx_b = nullptr, *rank = nullptr, *head = nullptr, *small = nullptr, *local = nullptr, *excl = nullptr;
+	FM_TRY(sc.get((void**)&t, n), "device memory for the text");
+	FM_TRY(sc.get((void**)&key_a, (size_t)n * 8), "device memory for the sort keys");
+	FM_TRY(sc.get((void**)&key_b, (size_t)n * 8), "device memory for the sort keys");
+	FM_TRY(sc.get((void**)&idx_a, (size_t)n * 4), "device memory for the suffixes");
+	FM_TRY(sc.get((void**)&idx_b, (size_t)n * 4), "device memory for the suffixes");
+	FM_TRY(sc.get((void**)&rank, (size_t)n * 4), "device memory for the ranks");
+	FM_TRY(sc.get((void**)&head, (size_t)n * 4), "device memory for the group heads");
+	FM_TRY(sc.get((void**)&small, 64), "device memory for the counters"); // [0] groups, [1] sentinel, [4..8) totals
+	FM_TRY(sc.get((void**)&local, (size_t)nb * 16), "device memory for the block counts");
+	FM_TRY(sc.get((void**)&excl, (size_t)nb * 16), "device memory for the block counts");
+	FM_TRY(hipMalloc((void**)&f->sa, (size_t)m * 4), "device memory for the suffix array");
+	FM_TRY(hipMalloc((void**)&f->bwt, m), "device memory for the BWT");
+	FM_TRY(hipMalloc((void**)&f->occ, (size_t)nb * sizeof(abg::FMBlock)), "device memory for the occurrence table");
+
+	size_t need_sort = 0, need_scan = 0, need_sum = 0;
+	FM_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need_sort, key_a, key_b, idx_a, idx_b, n, 0, 64, st), "sizing the sort");
+	FM_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, need_scan, head, idx_a, MaxOp(), n, st), "sizing the scan");
+	FM_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need_sum, local, excl, nb, st), "sizing the scan");
+	size_t tmp_bytes = std::max(need_sort, std::max(need_scan, need_sum));
+	void* tmp = nullptr;
+	FM_TRY(sc.get(&tmp, tmp_bytes), "device memory for the sort");
+
+	const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)n + 255) / 256, (uint64_t)f->cus * 8);
+	const unsigned grid_m = (unsigned)std::min<uint64_t>(((uint64_t)m + 255) / 256, (uint64_t)f->cus * 8);
+	const unsigned grid_b = (unsigned)std::min<uint64_t>(((uint64_t)nb + 255) / 256, (uint64_t)f->cus * 8);
+	unsigned bits = 1;
+	while (bits < 32 && (1ull << bits) <= (uint64_t)n + 1) bits++; // ranks are 1..n, 0 past the end
+
+	{
+		Timed tm(f, "fm_sa");
+		FM_TRY(hipMemcpyAsync(t, text, n, hipMemcpyHostToDevice, st), "copying the text to the device");
+		k_fm_encode<<<grid, 256, 0, st>>>(t, n);
+		k_fm_key_first<<<grid, 256, 0, st>>>(t, n, key_a, idx_a);
+		FM_TRY(hipGetLastError(), "the key kernel launch");
+		size_t tb = tmp_bytes;
+		FM_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key_a, key_b, idx_a, idx_b, n, 0, 3 * SYM0, st), "the radix sort");
+		// sorted: key_b, idx_b
+		for (uint64_t h = SYM0;; h *= 2) {
+			FM_TRY(hipMemsetAsync(small, 0, 4, st), "clearing the group count");
+			k_fm_heads<<<grid, 256, 0, st>>>(key_b, n, head, small);
+			tb = tmp_bytes;
+			FM_TRY(hipcub::DeviceScan::InclusiveScan(tmp, tb, head, idx_a, MaxOp(), n, st), "the rank scan"); // (idx_a: free until the next sort)
+			k_fm_scatter<<<grid, 256, 0, st>>>(idx_b, idx_a, n, rank);
+			uint32_t groups = 0;
+			FM_TRY(hipMemcpyAsync(&groups, small, 4, hipMemcpyDeviceToHost, st), "reading the group count");
+			FM_TRY(hipStreamSynchronize(st), "the ranking kernels");
+			if (groups == n || h >= n) break;
+			k_fm_key_next<<<grid, 256, 0, st>>>(idx_b, rank, n, (uint32_t)std::min<uint64_t>(h, n), bits, key_a);
+			FM_TRY(hipGetLastError(), "the key kernel launch");
+			tb = tmp_bytes;
+			FM_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key_a, key_b, idx_b, idx_a, n, 0, (int)(2 * bits), st), "the radix sort");
+			std::swap(idx_a, idx_b);
+		}
+	}
+	{
+		Timed tm(f, "fm_occ");
+		k_fm_bwt<<<grid_m, 256, 0, st>>>(t, idx_b, n, f->sa, f->bwt, small + 1);
+		k_fm_occ_fill<<<grid_b, 256, 0, st>>>(f->bwt, m, nb, f->occ, local);
+		FM_TRY(hipGetLastError(), "the table kernel launch");
+		for (int c = 0; c < 4; c++) {
+			size_t tb = tmp_bytes;
+			FM_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, local + (size_t)c * nb, excl + (size_t)c * nb, nb, st), "the count scan");
+		}
+		k_fm_occ_hdr<<<grid_b, 256, 0, st>>>(local, excl, nb, f->occ, small + 4);
+		FM_TRY(hipGetLastError(), "the table kernel launch");
+	}
+	uint32_t host_small[8] = { 0 };
+	FM_TRY(hipMemcpyAsync(host_small, small, 32, hipMemcpyDeviceToHost, st), "reading the symbol counts");
+	FM_TRY(hipStreamSynchronize(st), "building the index");
+	const uint32_t* tot = host_small + 4;
+	f->view.occ = f->occ;
+	f->view.m = m;
+	f->view.sent = host_small[1];
+	f->view.cf[0] = 1;
+	f->view.cf[1] = 1 + (n - tot[0] - tot[1] - tot[2] - tot[3]);
+	for (int c = 1; c < 4; c++) f->view.cf[c + 1] = f->view.cf[c] + tot[c - 1];
+	f->n = n;
+	return ABG_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int abg_fm_create(int device, abg_fm** out)
+{
+	if (!out) return ABG_EINVAL;
+	*out = nullptr;
+	int n = 0;
+	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); g_fm_create_error = "no HIP device available (abyss_amd has no CPU fallback)"; return ABG_ENODEV; }
+	if (device < 0 || device >= n) { g_fm_create_error = "HIP device ordinal out of range"; return ABG_ENODEV; }
+	abg_fm* f = new abg_fm;
+	f->device = device;
+	hipError_t e = hipSetDevice(device);
+	hipDeviceProp_t prop;
+	if (e == hipSuccess && hipGetDeviceProperties(&prop, device) == hipSuccess) f->cus = (uint32_t)prop.multiProcessorCount;
+	if (e == hipSuccess) e = hipStreamCreate(&f->stream);
+	if (e == hipSuccess) e = hipMalloc((void**)&f->ticket, 16);
+	if (e != hipSuccess) {
+		(void)hipGetLastError();
+		g_fm_create_error = std::string("creating the FM-index failed: ") + hipGetErrorString(e);
+		const int rc = fm_code_of(e);
+		delete f;
+		return rc;
+	}
+	*out = f;
+	return ABG_OK;
+}
+
+void abg_fm_destroy(abg_fm* f) { delete f; }
+const char* abg_fm_last_error(const abg_fm* f) { return f ? f->error.c_str() : g_fm_create_error.c_str(); }
+
+int abg_fm_build(abg_fm* f, const uint8_t* text, uint64_t n)
+{
+	if (!f || !text) return ABG_EINVAL;
+	if (n == 0) { f->error = "the text is empty"; return ABG_EINVAL; }
+	if (n >= 0xFFFFFFFFull) { f->error = "the text must be smaller than 4294967295 bytes (positions are 32-bit on the device)"; return ABG_EINVAL; }
+	(void)hipSetDevice(f->device);
+	(void)hipStreamSynchronize(f->stream);
+	f->drop_index();
+	const int rc = build_index(f, text, n);
+	if (rc != ABG_OK) { (void)hipStreamSynchronize(f->stream); f->drop_index(); }
+	return rc;
+}
+
+int abg_fm_size(const abg_fm* f, uint64_t* n)
+{
+	if (!f || !n) return ABG_EINVAL;
+	*n = f->n;
+	return ABG_OK;
+}
+
+int abg_fm_export(abg_fm* f, uint32_t* sa, uint8_t* bwt)
+{
+	if (!f) return ABG_EINVAL;
+	if (f->n == 0) { f->error = "no index has been built"; return ABG_EINVAL; }
+	(void)hipSetDevice(f->device);
+	const uint64_t m = f->n + 1;
+	hipError_t e = hipSuccess;
+	if (sa) e = hipMemcpyAsync(sa, f->sa, m * 4, hipMemcpyDeviceToHost, f->stream);
+	if (e == hipSuccess && bwt) e = hipMemcpyAsync(bwt, f->bwt, m, hipMemcpyDeviceToHost, f->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
+	if (!fm_ok(f, e, "copying the index to the host")) return fm_code_of(e);
+	if (bwt) for (uint64_t i = 0; i < m; i++) if (bwt[i] == abg::FM_SENT) bwt[i] = 255;
+	return ABG_OK;
+}
+
+int abg_fm_map_seqs(abg_fm* f, const char* seqs, const uint64_t* offsets, uint64_t n, uint32_t min_len, uint32_t flags, abg_fm_hit* out)
+{
+	if (!f || (n && (!seqs || !offsets || !out))) return ABG_EINVAL;
+	if (f->n == 0) { f->error = "no index has been built"; return ABG_EINVAL; }
+	if (flags & ~(uint32_t)(ABG_FM_NO_RC | ABG_FM_SS)) { f->error = "unknown flags"; return ABG_EINVAL; }
+	if (n == 0) return ABG_OK;
+	(void)hipSetDevice(f->device);
+	const uint64_t a = offsets[0], total = offsets[n] - a;
+	uint64_t longest = 1;
+	std::vector<uint64_t> rel(n + 1);
+	for (uint64_t i = 0; i <= n; i++) {
+		if (i && offsets[i] < offsets[i - 1]) { f->error = "the offsets decrease"; return ABG_EINVAL; }
+		rel[i] = offsets[i] - a;
+		if (i) longest = std::max(longest, offsets[i] - offsets[i - 1]);
+	}
+	if (longest >= 0xFFFFFFFFull) { f->error = "a sequence of 4294967295 characters or more"; return ABG_EINVAL; }
+	const size_t off_at = (total + 15) / 16 * 16, hit_at = off_at + (n + 1) * 8, need = hit_at + n * 2 * sizeof(abg::FMHit);
+	if (need > f->qcap) {
+		if (f->qdev) { (void)hipStreamSynchronize(f->stream); (void)hipFree(f->qdev); f->qdev = nullptr; f->qcap = 0; }
+		const size_t cap = std::max<size_t>(need, 1u << 20);
+		const hipError_t e = hipMalloc(&f->qdev, cap);
+		if (!fm_ok(f, e, "device memory for the reads")) return fm_code_of(e);
+		f->qcap = cap;
+	}
+	// lanes: f->waves waves a CU (abg_fm_tune), fewer where the memo of the call's longest read would pass 1 GiB, and no more than reads
+	uint64_t lanes = (uint64_t)f->cus * f->waves * 64;
+	lanes = std::min(lanes, std::max<uint64_t>(256, ((1ull << 30) / 8 / longest) / 256 * 256));
+	lanes = std::min(lanes, (n + 255) / 256 * 256);
+	const size_t entries = (size_t)lanes * longest;
+	if (entries > f->memo_cap) {
+		if (f->memo) { (void)hipStreamSynchronize(f->stream); (void)hipFree(f->memo); f->memo = nullptr; f->memo_cap = 0; }
+		hipError_t e = hipMalloc((void**)&f->memo, entries * 8);
+		if (!fm_ok(f, e, "device memory for the memo")) return fm_code_of(e);
+		f->memo_cap = entries;
+		e = hipMemsetAsync(f->memo, 0, entries * 8, f->stream); // (the kernel leaves it zero)
+		if (!fm_ok(f, e, "clearing the memo")) return fm_code_of(e);
+	}
+	char* base = (char*)f->qdev;
+	hipError_t e = hipMemcpyAsync(base, seqs + a, total, hipMemcpyHostToDevice, f->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(base + off_at, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, f->stream);
+	if (e == hipSuccess) e = hipMemsetAsync(f->ticket, 0, 16, f->stream);
+	if (!fm_ok(f, e, "copying the reads to the device")) return fm_code_of(e);
+	{
+		Timed t(f, "fm_map");
+		k_fm_map<<<(unsigned)(lanes / 256), 256, 0, f->stream>>>(f->view, f->sa, (const unsigned char*)base, (const uint64_t*)(base + off_at), n, min_len, flags,
+		    f->memo, (uint32_t)lanes, f->ticket, f->profiling ? f->ticket + 1 : nullptr, (abg::FMHit*)(base + hit_at));
+		e = hipGetLastError();
+		if (!fm_ok(f, e, "the search kernel launch")) return fm_code_of(e);
+	}
+	unsigned long long steps = 0;
+	e = hipMemcpyAsync(out, base + hit_at, n * 2 * sizeof(abg::FMHit), hipMemcpyDeviceToHost, f->stream);
+	if (e == hipSuccess && f->profiling) e = hipMemcpyAsync(&steps, f->ticket + 1, 8, hipMemcpyDeviceToHost, f->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(f->stream); // (also keeps `rel` alive until its copy is done)
+	if (!fm_ok(f, e, "reading the matches back")) return fm_code_of(e);
+	f->steps += steps;
+	return ABG_OK;
+}
+
+int abg_fm_tune(abg_fm* f, uint32_t waves_per_cu)
+{
+	if (!f) return ABG_EINVAL;
+	if (waves_per_cu > 32) { f->error = "at most 32 waves a CU"; return ABG_EINVAL; }
+	f->waves = waves_per_cu ? waves_per_cu : abg::FM_WAVES_PER_CU;
+	return ABG_OK;
+}
+
+int abg_fm_sync(abg_fm* f)
+{
+	if (!f) return ABG_EINVAL;
+	(void)hipSetDevice(f->device);
+	const hipError_t e = hipStreamSynchronize(f->stream);
+	return fm_ok(f, e, "hipStreamSynchronize") ? ABG_OK : fm_code_of(e);
+}
+
+int abg_fm_profile(abg_fm* f, int on)
+{
+	if (!f) return ABG_EINVAL;
+	f->profiling = on != 0;
+	return ABG_OK;
+}
+int abg_fm_profile_get(abg_fm* f, const char* name, double* total_ms, uint64_t* launches)
+{
+	if (!f || !name) return ABG_EINVAL;
+	(void)hipSetDevice(f->device);
+	prof_drain(f);
+	if (!strcmp(name, "fm_map_steps")) { // not a kernel: the search steps of the profiled abg_fm_map_seqs calls, as `launches`
+		if (total_ms) *total_ms = 0;
+		if (launches) *launches = f->steps;
+		return ABG_OK;
+	}
+	auto it = f->prof.find(name);
+	if (total_ms) *total_ms = it == f->prof.end() ? 0 : it->second.ms;
+	if (launches) *launches = it == f->prof.end() ? 0 : it->second.launches;
+	return ABG_OK;
+}
+
+} // extern "C"

@@ -1,0 +1,709 @@
+// map_core.h -- host side of the drop-in abyss-map and abyss-index (Map/map.cc, Map/index.cc): options, the FASTA index
+// (DataLayer/FastaIndex.h), the .fm file (FMIndex/FMIndex.h:512-565, FMIndex/BitArrays.h, bit_array.cc Save), the choice
+// between the strands (map.cc:363-383) and the SAM records (map.cc:206-242, Common/SAM.h:312-333).  The index itself and the
+// searches come from a Backend: abg_fm_* on the GPU in the binaries, the same bodies run serially in tests/hostcheck/fm_check.
+//
+// Not supported, refused with a message and status 1: alphabets other than -ACGT (-a, --alpha, --protein), abyss-map -d/--dup,
+// abyss-index --bwt2fm and -d/--decompress.  abyss-pe passes none of them.
+#pragma once
+#include "fasta_reader.h"
+
+#include <getopt.h>
+
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <functional>
+#include <future>
+#include <iomanip>
+#include <memory>
+#include <sstream>
+#include <string>
+#include <thread>
+#include <vector>
+
+#ifndef ABG_IO_VERSION
+#define ABG_IO_VERSION "2.3.10"
+#endif
+
+namespace abgmap {
+
+struct Hit { uint32_t l, u, qstart, qend, num, pos; }; // abg_fm_hit
+constexpr uint32_t FLAG_NORC = 1, FLAG_SS = 2;         // ABG_FM_NO_RC, ABG_FM_SS
+
+struct Backend {
+	virtual ~Backend() {}
+	// FMIndex::assign over the file's bytes
+	virtual bool build(const uint8_t* text, uint64_t n, std::string& err) = 0;
+	// SA and BWT (255 for the sentinel), n + 1 entries each
+	virtual bool exported(std::vector<uint32_t>& sa, std::vector<uint8_t>& bwt, std::string& err) = 0;
+	// findMatch of every read: out[2 * i] forward, out[2 * i + 1] reverse complement
+	virtual bool map(const char* seqs, const uint64_t* off, uint64_t n, uint32_t k, uint32_t flags, Hit* out, std::string& err) = 0;
+};
+typedef std::function<Backend*(std::string& err)> MakeBackend;
+
+inline std::string to_si(double n) // Common/StringUtil.h:32-47
+{
+	std::ostringstream s;
+	s << std::setprecision(3);
+	if (n < 1e3) s << n << ' ';
+	else if (n < 1e6) s << n / 1e3 << " k";
+	else if (n < 1e9) s << n / 1e6 << " M";
+	else if (n < 1e12) s << n / 1e9 << " G";
+	else s << n / 1e12 << " T";
+	return s.str();
+}
+
+inline bool read_file(const std::string& path, std::string& out)
+{
+	FILE* f = fopen(path.c_str(), "rb");
+	if (!f) return false;
+	out.clear();
+	char buf[1 << 16];
+	size_t got;
+	while ((got = fread(buf, 1, sizeof buf, f)) > 0) out.append(buf, got);
+	fclose(f);
+	return true;
+}
+[[noreturn]] inline void die_io(const std::string& path) // assert_good, Common/IOUtil.h:14-22
+{
+	fprintf(stderr, "error: `%s': %s\n", path.c_str(), strerror(errno));
+	exit(EXIT_FAILURE);
+}
+
+// ---------------------------------------------------------------------------------------------- the FASTA index
+struct FaiRecord { uint64_t offset = 0, size = 0; std::string id; };
+
+struct FastaIndex {
+	std::vector<FaiRecord> data;
+	uint64_t file_size() const { return data.back().offset + data.back().size + 1; }
+	// FastaIndex::index over the file's bytes: one header line, one sequence line a record.  False (with why) where the
+	// reference fails an assertion.
+	bool index(const std::string& text, std::string& why)
+	{
+		data.clear();
+		size_t p = 0;
+		const size_t n = text.size();
+		auto skip_ws = [&]() { while (p < n && isspace((unsigned char)text[p])) p++; };
+		for (;;) {
+			skip_ws();
+			if (p >= n) break;
+			const char c = text[p++];
+			skip_ws();
+			if (p >= n) break;
+			size_t e = p;
+			while (e < n && !isspace((unsigned char)text[e])) e++;
+			const std::string id = text.substr(p, e - p);
+			p = e;
+			while (p < n && text[p] != '\n') p++;
+			if (c != '>') { why = "expected `>' at the start of a record"; return false; }
+			if (p >= n) { why = "the record `" + id + "' has no sequence line"; return false; }
+			p++;
+			const size_t offset = p;
+			while (p < n && text[p] != '\n') p++;
+			size_t got = p - offset;
+			if (p < n) { p++; got++; }
+			if (got == 0) { why = "the record `" + id + "' has no sequence line"; return false; }
+			FaiRecord r;
+			r.offset = offset; r.size = got - 1; r.id = id;
+			data.push_back(r);
+		}
+		return true;
+	}
+	// operator>> of a .fai
+	bool parse(const std::string& text, std::string& why)
+	{
+		data.clear();
+		std::istringstream in(text);
+		FaiRecord r;
+		uint64_t lineLen, lineBinLen;
+		while (in >> r.id >> r.size >> r.offset >> lineLen >> lineBinLen) {
+			if (!(r.size == lineLen || lineLen == lineBinLen)) { why = "a record of the FASTA index has more than one sequence line"; return false; }
+			if (!data.empty() && r.offset <= data.back().offset) { why = "the FASTA index is not sorted by offset"; return false; }
+			data.push_back(r);
+			in.ignore(std::numeric_limits<std::streamsize>::max(), '\n');
+		}
+		if (!in.eof()) { why = "the FASTA index is malformed"; return false; }
+		if (data.empty()) { why = "the FASTA index is empty"; return false; }
+		return true;
+	}
+	std::string to_string() const
+	{
+		std::ostringstream out;
+		for (const FaiRecord& r : data) out << r.id << '\t' << r.size << '\t' << r.offset << '\t' << r.size << '\t' << r.size + 1 << '\n';
+		return out.str();
+	}
+	// a file offset -> (record, position); NULL where the reference's assertions fail (the offset lies in a header line)
+	const FaiRecord* find(uint64_t offset, uint64_t& pos) const
+	{
+		size_t lo = 0, hi = data.size(); // upper_bound by offset
+		while (lo < hi) { const size_t mid = (lo + hi) / 2; if (offset < data[mid].offset) hi = mid; else lo = mid + 1; }
+		if (lo == 0) return nullptr;
+		const FaiRecord& r = data[lo - 1];
+		if (!(offset < r.offset + r.size)) return nullptr;
+		pos = offset - r.offset;
+		return &r;
+	}
+};
+
+// ---------------------------------------------------------------------------------------------- the .fm file
+#define ABG_FM_VERSION "FM 64 1"
+static const char FM_ALPHABET[] = "-ACGT";
+
+// operator<< of an FMIndex over the alphabet -ACGT: SA sampled every `period`, one bit array per code up to the highest present
+inline void write_fm(FILE* out, unsigned period, const std::vector<uint32_t>& sa, const std::vector<uint8_t>& bwt)
+{
+	const uint64_t m = sa.size();
+	std::string head = std::string(ABG_FM_VERSION) + "\n" + std::to_string(period) + "\n5\n" + FM_ALPHABET;
+	const uint64_t ns = (m + period - 1) / period;
+	head += std::to_string(ns) + "\n";
+	fwrite(head.data(), 1, head.size(), out);
+	std::vector<uint64_t> s(ns);
+	for (uint64_t i = 0; i < ns; i++) s[i] = sa[i * period];
+	fwrite(s.data(), 8, ns, out);
+	unsigned top = 0;
+	for (uint64_t i = 0; i < m; i++) if (bwt[i] != 255 && bwt[i] > top) top = bwt[i];
+	const uint32_t arrays = top + 1;
+	fwrite(&arrays, 4, 1, out);
+	std::vector<uint64_t> words((m + 63) / 64);
+	for (unsigned c = 0; c < arrays; c++) {
+		std::fill(words.begin(), words.end(), 0);
+		for (uint64_t i = 0; i < m; i++) if (bwt[i] == c) words[i >> 6] |= 1ull << (i & 63);
+		fwrite(&m, 8, 1, out);
+		fwrite(words.data(), 8, words.size(), out);
+	}
+}
+
+// what abyss-map needs of a .fm: the version check of operator>> (exits as the reference), the alphabet, FMIndex::size()
+inline uint64_t read_fm_size(const char* program, const std::string& path)
+{
+	FILE* f = fopen(path.c_str(), "rb");
+	if (!f) die_io(path);
+	auto line = [&]() { std::string s; int c; while ((c = getc(f)) != EOF && c != '\n') s += (char)c; return s; };
+	const std::string version = line();
+	if (version != ABG_FM_VERSION) {
+		fprintf(stderr, "error: the version of this FM-index, `%s', does not match the version required by this program, `" ABG_FM_VERSION "'.\n", version.c_str());
+		exit(EXIT_FAILURE);
+	}
+	auto bad = [&]() { fprintf(stderr, "%s: `%s': the FM-index is truncated or malformed\n", program, path.c_str()); exit(EXIT_FAILURE); };
+	line(); // the sample period: the full suffix array is rebuilt on the device
+	const unsigned long long na = strtoull(line().c_str(), nullptr, 10);
+	std::string alphabet(na < 256 ? na : 0, '\0');
+	if (na == 0 || na >= 256 || fread(&alphabet[0], 1, na, f) != na) bad();
+	if (alphabet != FM_ALPHABET) {
+		fprintf(stderr, "%s: `%s': alphabets other than `" "-ACGT" "' are not supported\n", program, path.c_str());
+		exit(EXIT_FAILURE);
+	}
+	const unsigned long long ns = strtoull(line().c_str(), nullptr, 10);
+	if (fseeko(f, (off_t)(ns * 8), SEEK_CUR) != 0) bad();
+	uint32_t arrays = 0;
+	uint64_t length = 0;
+	if (fread(&arrays, 4, 1, f) != 1 || arrays == 0 || fread(&length, 8, 1, f) != 1 || length == 0) bad();
+	fclose(f);
+	return length - 1;
+}
+
+// ---------------------------------------------------------------------------------------------- abyss-map
+#define ABG_MAP_PROGRAM "abyss-map"
+
+static const char MAP_USAGE[] =
+"Usage: " ABG_MAP_PROGRAM " [OPTION]... QUERY... TARGET\n"
+"Map the sequences of the files QUERY to those of the file TARGET.\n"
+"The index files TARGET.fai and TARGET.fm will be used if present.\n"
+"\n"
+" Options:\n"
+"\n"
+"  -l, --min-align=N       find matches at least N bp [1]\n"
+"  -j, --threads=N         format SAM on N threads, 16 at the most [1]\n"
+"                          (the queries are parsed on one thread)\n"
+"  -C, --append-comment    append the FASTA/FASTQ comment to the SAM tags\n"
+"  -s, --sample=N          sample the suffix array [1]\n"
+"      --order             print alignments in the same order as\n"
+"                          read from QUERY [always]\n"
+"      --no-order          accepted; the order is kept all the same\n"
+"      --SS                expect contigs to be oriented correctly\n"
+"      --no-SS             no assumption about contig orientation\n"
+"      --rc                map the sequence and its reverse complement [default]\n"
+"      --no-rc             do not map the reverse complement sequence\n"
+"      --dna               the alphabet -ACGT [the only one supported]\n"
+"      --chastity          discard unchaste reads\n"
+"      --no-chastity       do not discard unchaste reads [default]\n"
+"  -v, --verbose           display verbose output\n"
+"      --help              display this help and exit\n"
+"      --version           output version information and exit\n"
+"      --db=FILE --library=NAME --strain=NAME --species=NAME\n"
+"                          accepted and ignored\n"
+"\n"
+"Not supported: -d/--dup, -a/--alphabet, --alpha, --protein, --multi.\n";
+
+struct MapOptions {
+	unsigned k = 0, threads = 1, sampleSA = 0;
+	int appendComment = 0, ss = 0, norc = 0, multi = 0, order = 0, chastity = 0, verbose = 0;
+	std::vector<std::string> queries;
+	std::string target, commandLine;
+};
+
+// false: leave with *status (help, version, or an error already reported)
+inline bool parse_map_options(int argc, char** argv, MapOptions& o, int* status)
+{
+	for (int i = 0; i < argc; i++) { if (i) o.commandLine += ' '; o.commandLine += argv[i]; }
+	enum { OPT_HELP = 1, OPT_VERSION, OPT_ALPHA, OPT_DNA, OPT_PROTEIN, OPT_DB, OPT_LIBRARY, OPT_STRAIN, OPT_SPECIES };
+	const struct option longopts[] = {
+		{ "append-comment", no_argument, NULL, 'C' }, { "sample", required_argument, NULL, 's' },
+		{ "min-align", required_argument, NULL, 'l' }, { "dup", no_argument, NULL, 'd' }, { "threads", required_argument, NULL, 'j' },
+		{ "order", no_argument, &o.order, 1 }, { "no-order", no_argument, &o.order, 0 },
+		{ "multi", no_argument, &o.multi, 1 }, { "no-multi", no_argument, &o.multi, 0 },
+		{ "SS", no_argument, &o.ss, 1 }, { "no-SS", no_argument, &o.ss, 0 },
+		{ "rc", no_argument, &o.norc, 0 }, { "no-rc", no_argument, &o.norc, 1 },
+		{ "alphabet", optional_argument, NULL, 'a' }, { "alpha", optional_argument, NULL, OPT_ALPHA },
+		{ "dna", optional_argument, NULL, OPT_DNA }, { "protein", optional_argument, NULL, OPT_PROTEIN },
+		{ "decompress", no_argument, NULL, 'd' }, { "verbose", no_argument, NULL, 'v' },
+		{ "chastity", no_argument, &o.chastity, 1 }, { "no-chastity", no_argument, &o.chastity, 0 },
+		{ "help", no_argument, NULL, OPT_HELP }, { "version", no_argument, NULL, OPT_VERSION },
+		{ "db", required_argument, NULL, OPT_DB }, { "library", required_argument, NULL, OPT_LIBRARY },
+		{ "strain", required_argument, NULL, OPT_STRAIN }, { "species", required_argument, NULL, OPT_SPECIES },
+		{ NULL, 0, NULL, 0 }
+	};
+	bool die = false;
+	const char* refused = nullptr;
+	optind = 1;
+	for (int c; (c = getopt_long(argc, argv, "Cj:k:l:s:dva:", longopts, NULL)) != -1;) {
+		std::istringstream arg(optarg != NULL ? optarg : "");
+		switch (c) {
+		case '?': die = true; break;
+		case 'C': o.appendComment = 1; break;
+		case 'j': arg >> o.threads; break;
+		case 'k': case 'l': arg >> o.k; break;
+		case 's': arg >> o.sampleSA; break;
+		case 'd': refused = "-d, --dup (duplicate identification)"; break;
+		case 'a': refused = "-a, --alphabet (alphabets other than `-ACGT')"; arg.clear(std::ios::eofbit); break;
+		case OPT_ALPHA: refused = "--alpha (alphabets other than `-ACGT')"; arg.clear(std::ios::eofbit); break;
+		case OPT_PROTEIN: refused = "--protein (alphabets other than `-ACGT')"; arg.clear(std::ios::eofbit); break;
+		case OPT_DNA: o.norc = 0; arg.clear(std::ios::eofbit); break;
+		case 'v': o.verbose++; break;
+		case OPT_HELP: fputs(MAP_USAGE, stdout); *status = EXIT_SUCCESS; return false;
+		case OPT_VERSION: fputs(ABG_MAP_PROGRAM " (ABySS, abyss_amd) " ABG_IO_VERSION "\n", stdout); *status = EXIT_SUCCESS; return false;
+		case OPT_DB: case OPT_LIBRARY: case OPT_STRAIN: case OPT_SPECIES: {
+			std::string s; arg >> s;
+			fprintf(stderr, ABG_MAP_PROGRAM ": warning: the database options are ignored (built without sqlite)\n");
+			break;
+		}
+		}
+		if (optarg != NULL && !arg.eof()) {
+			fprintf(stderr, ABG_MAP_PROGRAM ": invalid option: `-%c%s'\n", (char)c, optarg);
+			*status = EXIT_FAILURE;
+			return false;
+		}
+	}
+	*status = EXIT_FAILURE;
+	if (refused) {
+		fprintf(stderr, ABG_MAP_PROGRAM ": %s is not supported\n", refused);
+		return false;
+	}
+	if (o.multi) {
+		fprintf(stderr, ABG_MAP_PROGRAM ": multiple alignments not supported with this install. Recompile ABySS with `./configure --enable-samseqqual'.\n");
+		die = true;
+	}
+	if (argc - optind < 2) {
+		fprintf(stderr, ABG_MAP_PROGRAM ": missing arguments\n");
+		die = true;
+	}
+	if (die) {
+		fprintf(stderr, "Try `" ABG_MAP_PROGRAM " --help' for more information.\n");
+		return false;
+	}
+	o.target = argv[argc - 1];
+	for (int i = optind; i < argc - 1; i++) o.queries.push_back(argv[i]);
+	return true;
+}
+
+struct Record { std::string id, comment, seq; };
+
+// FastaInterleave: one record from each file in turn, an exhausted file is skipped
+struct Interleave {
+	std::vector<std::unique_ptr<abghost::FastaReader>> streams;
+	size_t next = 0;
+	Interleave(const std::vector<std::string>& paths, const abghost::ReaderOptions& ro)
+	{
+		for (const std::string& p : paths) streams.emplace_back(new abghost::FastaReader(p, ro));
+	}
+	bool read(Record& r)
+	{
+		for (size_t i = 0; i < streams.size(); i++) {
+			const bool good = streams[next]->read(r.id, r.comment, r.seq);
+			if (++next == streams.size()) next = 0;
+			if (good) return true;
+		}
+		return false;
+	}
+};
+
+struct Block {
+	std::vector<Record> recs;
+	std::string seqs;
+	std::vector<uint64_t> off;
+	bool last = false;
+	std::string error; // what ends the run after the records before it are printed
+};
+
+inline void read_block(Interleave& in, size_t max_reads, size_t max_bytes, Block& b)
+{
+	b.recs.clear(); b.seqs.clear(); b.off.assign(1, 0); b.last = false; b.error.clear();
+	Record r;
+	while (b.recs.size() < max_reads && b.seqs.size() < max_bytes) {
+		if (!in.read(r)) { b.last = true; return; }
+		if (r.seq.empty()) { b.error = ABG_MAP_PROGRAM ": error: the sequence `" + r.id + "' is empty\n"; b.last = true; return; }
+		if (!r.id.empty() && r.id[0] == '@') {
+			b.error = ABG_MAP_PROGRAM ": error: the query ID `" + r.id + "' is invalid since it begins with `@'\n";
+			b.last = true;
+			return;
+		}
+		b.seqs += r.seq;
+		b.off.push_back(b.seqs.size());
+		b.recs.push_back(r);
+	}
+}
+
+struct Counts { uint64_t unique = 0, multimapped = 0, unmapped = 0, suboptimal = 0, subunmapped = 0; };
+
+// find() of map.cc:363-383 and toSAM for one read; false where the match lies outside every sequence line
+inline bool format_read(const MapOptions& o, const FastaIndex& fai, const Record& rec, Hit m, Hit rcm, std::string& out, Counts& cnt, std::string& why)
+{
+	auto span = [](const Hit& h) { return h.qend - h.qstart; };
+	auto size = [](const Hit& h) { return h.u - h.l; };
+	bool rc;
+	if (o.ss) {
+		rc = rec.id.size() > 2 && rec.id.compare(rec.id.size() - 2, 2, "/1") == 0;
+		const bool prc = span(rcm) > span(m);
+		if (prc != rc && ((rc && size(rcm) > 0) || (!rc && size(m) > 0))) cnt.suboptimal++;
+		if (prc != rc && ((rc && size(rcm) == 0 && size(m) > 0) || (!rc && size(m) == 0 && size(rcm) > 0))) cnt.subunmapped++;
+	} else {
+		rc = span(rcm) > span(m);
+		if (span(rcm) == span(m)) { if (rc) rcm.num += m.num; else m.num += rcm.num; }
+	}
+	const Hit& mm = rc ? rcm : m;
+	const unsigned qlength = (unsigned)rec.seq.size();
+	char buf[64];
+	out += rec.id;
+	unsigned mapq = 0;
+	bool unmapped = false;
+	if (size(mm) == 0) {
+		out += "\t4\t*\t0\t0\t*";
+		unmapped = true;
+	} else {
+		uint64_t pos = 0;
+		const FaiRecord* r = fai.find(mm.pos, pos);
+		if (!r) {
+			why = "the match of `" + rec.id + "' at offset " + std::to_string(mm.pos) + " of the target file lies in a header line, not in a sequence "
+			    "(-l is no larger than a run of ACGT letters in an ID)";
+			return false;
+		}
+		const unsigned matches = mm.qend - mm.qstart;
+		mapq = size(mm) > 1 || mm.num > 1 ? 0 : std::min(matches, 254u);
+		snprintf(buf, sizeof buf, "\t%u\t", rc ? 16u : 0u);
+		out += buf;
+		out += r->id;
+		snprintf(buf, sizeof buf, "\t%d\t%u\t", (int)(1 + (int)pos), mapq);
+		out += buf;
+		if (mm.qstart > 0) { snprintf(buf, sizeof buf, "%uS", mm.qstart); out += buf; }
+		snprintf(buf, sizeof buf, "%uM", matches);
+		out += buf;
+		if (mm.qend < qlength) { snprintf(buf, sizeof buf, "%uS", qlength - mm.qend); out += buf; }
+	}
+	out += unmapped ? "\t=\t0\t0\t*\t*" : "\t*\t0\t0\t*\t*"; // (mrnm `*' equals the rname of an unmapped read: SAM.h prints `=')
+	if (o.appendComment && !rec.comment.empty()) {
+		out += '\t';
+		out += rec.comment;
+	} else if (rec.comment.compare(0, 5, "BX:Z:") == 0) {
+		size_t i = rec.comment.find_first_of("\t ");
+		if (i == std::string::npos) i = rec.comment.size();
+		out += '\t';
+		out.append(rec.comment, 0, i);
+	}
+	out += '\n';
+	if (unmapped) cnt.unmapped++;
+	else if (mapq == 0) cnt.multimapped++;
+	else cnt.unique++;
+	return true;
+}
+
+// (float)100 * a / total through cerr, which the reference's -v memory lines have left at setprecision(3) by then
+inline std::string percent(uint64_t a, uint64_t total)
+{
+	std::ostringstream s;
+	s << std::setprecision(3) << (float)100 * a / total;
+	return s.str();
+}
+
+inline int map_main(int argc, char** argv, const MakeBackend& make)
+{
+	MapOptions o;
+	int status = 0;
+	if (!parse_map_options(argc, argv, o, &status)) return status;
+	const std::string fmPath = o.target + ".fm", faiPath = o.target + ".fai";
+
+	// the FASTA index
+	std::string text, why;
+	FastaIndex fai;
+	{
+		std::string faiText;
+		if (read_file(faiPath, faiText)) {
+			if (o.verbose > 0) fprintf(stderr, "Reading `%s'...\n", faiPath.c_str());
+			if (!fai.parse(faiText, why)) { fprintf(stderr, ABG_MAP_PROGRAM ": `%s': %s\n", faiPath.c_str(), why.c_str()); return EXIT_FAILURE; }
+			if (!read_file(o.target, text)) die_io(o.target);
+		} else {
+			if (o.verbose > 0) fprintf(stderr, "Reading `%s'...\n", o.target.c_str());
+			if (!read_file(o.target, text)) die_io(o.target);
+			if (!fai.index(text, why) || fai.data.empty()) {
+				if (why.empty()) why = "no sequences";
+				fprintf(stderr, ABG_MAP_PROGRAM ": `%s': %s\n", o.target.c_str(), why.c_str());
+				return EXIT_FAILURE;
+			}
+		}
+	}
+	// the FM-index: the checks a .fm file would get, then the index is built on the device (the suffix array of a text is unique)
+	uint64_t fmSize = text.size();
+	FILE* probe = fopen(fmPath.c_str(), "rb");
+	const bool haveFm = probe != nullptr;
+	if (probe) fclose(probe);
+	if (haveFm) {
+		if (o.verbose > 0) fprintf(stderr, "Reading `%s'...\n", fmPath.c_str());
+		fmSize = read_fm_size(ABG_MAP_PROGRAM, fmPath);
+	} else if (o.verbose > 0)
+		fprintf(stderr, "Reading `%s'...\n", o.target.c_str());
+	if (text.empty()) { fprintf(stderr, ABG_MAP_PROGRAM ": `%s' is empty\n", o.target.c_str()); return EXIT_FAILURE; }
+	// checkIndexes, map.cc:533-553 (made before the device work; the reference makes them after loading)
+	auto stale = [&]() -> bool {
+		if (fmSize != text.size()) {
+			fprintf(stderr, ABG_MAP_PROGRAM ": `%s': The size of the FM-index, %llu B, does not match the size of the FASTA file, %llu B. The index is likely stale.\n",
+			    o.target.c_str(), (unsigned long long)fmSize, (unsigned long long)text.size());
+			return true;
+		}
+		if (fai.file_size() != text.size()) {
+			fprintf(stderr, ABG_MAP_PROGRAM ": `%s': The size of the FASTA index, %llu B, does not match the size of the FASTA file, %llu B. The index is likely stale.\n",
+			    o.target.c_str(), (unsigned long long)fai.file_size(), (unsigned long long)text.size());
+			return true;
+		}
+		return false;
+	};
+	const bool is_stale = stale();
+	std::string err;
+	std::unique_ptr<Backend> be;
+	if (!is_stale) {
+		be.reset(make(err));
+		if (!be) { fprintf(stderr, ABG_MAP_PROGRAM ": %s\n", err.c_str()); return EXIT_FAILURE; }
+		if (!haveFm) fputs("Building the suffix array...\nBuilding the Burrows-Wheeler transform...\nBuilding the character occurrence table...\n", stderr);
+		if (!be->build((const uint8_t*)text.data(), text.size(), err)) { fprintf(stderr, ABG_MAP_PROGRAM ": `%s': %s\n", o.target.c_str(), err.c_str()); return EXIT_FAILURE; }
+	}
+	if (o.verbose > 0) fprintf(stderr, "Read %sB in %zu contigs.\n", to_si((double)fmSize).c_str(), fai.data.size());
+	if (is_stale) return EXIT_FAILURE;
+	std::string().swap(text);
+
+	// the SAM header
+	{
+		std::string h = "@HD\tVN:1.4\n@PG\tID:" ABG_MAP_PROGRAM "\tPN:" ABG_MAP_PROGRAM "\tVN:" ABG_IO_VERSION "\tCL:" + o.commandLine + "\n";
+		for (const FaiRecord& r : fai.data) h += "@SQ\tSN:" + r.id + "\tLN:" + std::to_string(r.size) + "\n";
+		fwrite(h.data(), 1, h.size(), stdout);
+		fflush(stdout);
+	}
+
+	abghost::ReaderOptions ro;
+	ro.chastityFilter = o.chastity;
+	ro.trimMasked = 0;
+	ro.foldCase = 1;
+	Interleave in(o.queries, ro);
+	const unsigned threads = std::max(1u, std::min(o.threads, 16u));
+	const char* env = getenv("ABG_MAP_BLOCK_READS");
+	const size_t max_reads = env && atol(env) > 0 ? (size_t)atol(env) : (size_t)1 << 20, max_bytes = (size_t)256 << 20;
+	const uint32_t flags = (o.norc ? FLAG_NORC : 0) | (o.ss ? FLAG_SS : 0);
+	Counts total;
+	std::vector<Hit> hits;
+	// maps one block and prints its records; -1 to go on, else the status to leave with
+	auto process = [&](Block& b) -> int {
+		const size_t n = b.recs.size();
+		hits.resize(2 * n);
+		if (n && !be->map(b.seqs.data(), b.off.data(), n, o.k, flags, hits.data(), err)) {
+			fprintf(stderr, ABG_MAP_PROGRAM ": %s\n", err.c_str());
+			return EXIT_FAILURE;
+		}
+		// SAM on up to 16 threads, in order
+		const unsigned T = (unsigned)std::min<size_t>(threads, n / 64 + 1);
+		std::vector<std::string> parts(T), whys(T);
+		std::vector<Counts> cnts(T);
+		std::vector<char> failed(T, 0);
+		auto work = [&](unsigned t) {
+			const size_t a = n * t / T, e = n * (t + 1) / T;
+			parts[t].reserve((e - a) * 64);
+			for (size_t i = a; i < e; i++)
+				if (!format_read(o, fai, b.recs[i], hits[2 * i], hits[2 * i + 1], parts[t], cnts[t], whys[t])) { failed[t] = 1; break; }
+		};
+		std::vector<std::thread> pool;
+		for (unsigned t = 1; t < T; t++) pool.emplace_back(work, t);
+		work(0);
+		for (auto& th : pool) th.join();
+		for (unsigned t = 0; t < T; t++) {
+			// (a record that failed had only its name appended: cut back to the last whole line)
+			if (failed[t]) parts[t].erase(parts[t].rfind('\n') == std::string::npos ? 0 : parts[t].rfind('\n') + 1);
+			fwrite(parts[t].data(), 1, parts[t].size(), stdout);
+			total.unique += cnts[t].unique; total.multimapped += cnts[t].multimapped; total.unmapped += cnts[t].unmapped;
+			total.suboptimal += cnts[t].suboptimal; total.subunmapped += cnts[t].subunmapped;
+			if (failed[t]) {
+				fflush(stdout);
+				fprintf(stderr, ABG_MAP_PROGRAM ": error: %s\n", whys[t].c_str());
+				return EXIT_FAILURE;
+			}
+		}
+		if (!b.error.empty()) {
+			fflush(stdout);
+			fputs(b.error.c_str(), stderr);
+			return EXIT_FAILURE;
+		}
+		return -1;
+	};
+	// A block is mapped and printed on a thread of its own while this thread, which made the readers and so holds their streams'
+	// locks, parses the next one.  The reader leaves through exit() on a malformed file: exit() then waits for the block in flight.
+	static std::shared_future<int> busy;
+	atexit([]() { if (busy.valid()) busy.wait(); });
+	Block blocks[2];
+	int cur = 0;
+	read_block(in, max_reads, max_bytes, blocks[cur]);
+	for (;;) {
+		Block& b = blocks[cur];
+		busy = std::async(std::launch::async, process, std::ref(b)).share();
+		if (!b.last) read_block(in, max_reads, max_bytes, blocks[cur ^ 1]);
+		const int st = busy.get();
+		if (st >= 0) return st;
+		if (b.last) break;
+		cur ^= 1;
+	}
+	if (o.verbose > 0) {
+		const uint64_t unique = total.unique, mapped = unique + total.multimapped, all = mapped + total.unmapped;
+		fprintf(stderr, "Mapped %llu of %llu reads (%s%%)\nMapped %llu of %llu reads uniquely (%s%%)\n", (unsigned long long)mapped, (unsigned long long)all,
+		    percent(mapped, all).c_str(), (unsigned long long)unique, (unsigned long long)all, percent(unique, all).c_str());
+		if (o.ss)
+			fprintf(stderr, "Mapped %llu (%s%%) reads to the opposite strand of the optimal mapping.\nMade %llu (%s%%) unmapped suboptimal decisions.\n",
+			    (unsigned long long)total.suboptimal, percent(total.suboptimal, all).c_str(), (unsigned long long)total.subunmapped,
+			    percent(total.subunmapped, all).c_str());
+	}
+	fflush(stdout);
+	return ferror(stdout) ? EXIT_FAILURE : EXIT_SUCCESS;
+}
+
+// ---------------------------------------------------------------------------------------------- abyss-index
+#define ABG_INDEX_PROGRAM "abyss-index"
+
+static const char INDEX_USAGE[] =
+"Usage: " ABG_INDEX_PROGRAM " [OPTION]... FILE\n"
+"Build an FM-index of FILE and store it in FILE.fm.\n"
+"\n"
+" Options:\n"
+"\n"
+"      --both              build both FAI and FM indexes [default]\n"
+"      --fai               build a FAI index\n"
+"      --fm                build a FM index\n"
+"      --fa2bwt            accepted: the same files\n"
+"      --dna               the alphabet -ACGT [the only one supported]\n"
+"  -s, --sample=N          sample the suffix array [16]\n"
+"  -c, --stdout            write output to standard output\n"
+"  -v, --verbose           display verbose output\n"
+"      --help              display this help and exit\n"
+"      --version           output version information and exit\n"
+"\n"
+"Not supported: --bwt2fm, -d/--decompress, -a/--alphabet, --alpha, --protein.\n";
+
+inline int index_main(int argc, char** argv, const MakeBackend& make)
+{
+	enum { NONE, FAI, FM, BOTH };
+	int indexes = BOTH, fa2bwt = 0, bwt2fm = 0, verbose = 0;
+	unsigned sampleSA = 16;
+	bool toStdout = false;
+	enum { OPT_HELP = 1, OPT_VERSION, OPT_ALPHA, OPT_DNA, OPT_PROTEIN };
+	const struct option longopts[] = {
+		{ "both", no_argument, &indexes, BOTH }, { "fai", no_argument, &indexes, FAI }, { "fm", no_argument, &indexes, FM },
+		{ "fa2bwt", no_argument, &fa2bwt, 1 }, { "bwt2fm", no_argument, &bwt2fm, 1 },
+		{ "alphabet", optional_argument, NULL, 'a' }, { "alpha", optional_argument, NULL, OPT_ALPHA },
+		{ "dna", optional_argument, NULL, OPT_DNA }, { "protein", optional_argument, NULL, OPT_PROTEIN },
+		{ "decompress", no_argument, NULL, 'd' }, { "sample", required_argument, NULL, 's' }, { "stdout", no_argument, NULL, 'c' },
+		{ "verbose", no_argument, NULL, 'v' },
+		{ "help", no_argument, NULL, OPT_HELP }, { "version", no_argument, NULL, OPT_VERSION },
+		{ NULL, 0, NULL, 0 }
+	};
+	bool die = false;
+	const char* refused = nullptr;
+	optind = 1;
+	for (int c; (c = getopt_long(argc, argv, "a:cds:v", longopts, NULL)) != -1;) {
+		std::istringstream arg(optarg != NULL ? optarg : "");
+		switch (c) {
+		case '?': die = true; break;
+		case 'a': refused = "-a, --alphabet (alphabets other than `-ACGT')"; arg.clear(std::ios::eofbit); break;
+		case OPT_ALPHA: refused = "--alpha (alphabets other than `-ACGT')"; arg.clear(std::ios::eofbit); break;
+		case OPT_PROTEIN: refused = "--protein (alphabets other than `-ACGT')"; arg.clear(std::ios::eofbit); break;
+		case OPT_DNA: arg.clear(std::ios::eofbit); break;
+		case 'c': toStdout = true; break;
+		case 'd': refused = "-d, --decompress"; break;
+		case 's': arg >> sampleSA; break;
+		case 'v': verbose++; break;
+		case OPT_HELP: fputs(INDEX_USAGE, stdout); return EXIT_SUCCESS;
+		case OPT_VERSION: fputs(ABG_INDEX_PROGRAM " (ABySS, abyss_amd) " ABG_IO_VERSION "\n", stdout); return EXIT_SUCCESS;
+		}
+		if (optarg != NULL && !arg.eof()) {
+			fprintf(stderr, ABG_INDEX_PROGRAM ": invalid option: `-%c%s'\n", (char)c, optarg);
+			return EXIT_FAILURE;
+		}
+	}
+	if (bwt2fm) refused = "--bwt2fm";
+	if (refused) {
+		fprintf(stderr, ABG_INDEX_PROGRAM ": %s is not supported\n", refused);
+		return EXIT_FAILURE;
+	}
+	if (argc - optind < 1) { fprintf(stderr, ABG_INDEX_PROGRAM ": missing arguments\n"); die = true; }
+	if (argc - optind > 1) { fprintf(stderr, ABG_INDEX_PROGRAM ": too many arguments\n"); die = true; }
+	if (die) {
+		fprintf(stderr, "Try `" ABG_INDEX_PROGRAM " --help' for more information.\n");
+		return EXIT_FAILURE;
+	}
+	if (sampleSA == 0) { fprintf(stderr, ABG_INDEX_PROGRAM ": -s must be at least 1\n"); return EXIT_FAILURE; }
+	const std::string path = argv[optind];
+	std::string text, why;
+	bool have = false;
+	if (indexes & FAI) {
+		const std::string faiPath = path + ".fai";
+		fprintf(stderr, "Reading `%s'...\n", path.c_str());
+		if (!read_file(path, text)) die_io(path);
+		have = true;
+		FastaIndex fai;
+		if (!fai.index(text, why)) { fprintf(stderr, ABG_INDEX_PROGRAM ": `%s': %s\n", path.c_str(), why.c_str()); return EXIT_FAILURE; }
+		if (verbose > 0) fprintf(stderr, "Read %zu contigs.\n", fai.data.size());
+		fprintf(stderr, "Writing `%s'...\n", faiPath.c_str());
+		FILE* out = fopen(faiPath.c_str(), "wb");
+		if (!out) die_io(faiPath);
+		const std::string s = fai.to_string();
+		if (fwrite(s.data(), 1, s.size(), out) != s.size() || fclose(out) != 0) die_io(faiPath);
+	}
+	if ((indexes & FM) == 0) return EXIT_SUCCESS;
+	if (verbose > 0) fprintf(stderr, "Reading `%s'...\n", path.c_str());
+	if (!have && !read_file(path, text)) die_io(path);
+	if (text.empty()) { fprintf(stderr, ABG_INDEX_PROGRAM ": `%s' is empty\n", path.c_str()); return EXIT_FAILURE; }
+	std::string err;
+	std::unique_ptr<Backend> be(make(err));
+	if (!be) { fprintf(stderr, ABG_INDEX_PROGRAM ": %s\n", err.c_str()); return EXIT_FAILURE; }
+	if (fa2bwt) fputs("Building the Burrows-Wheeler transform...\nBuilding the character occurrence table...\nBuilding the suffix array...\n", stderr);
+	else fputs("Building the suffix array...\nBuilding the Burrows-Wheeler transform...\nBuilding the character occurrence table...\n", stderr);
+	std::vector<uint32_t> sa;
+	std::vector<uint8_t> bwt;
+	if (!be->build((const uint8_t*)text.data(), text.size(), err) || !be->exported(sa, bwt, err)) {
+		fprintf(stderr, ABG_INDEX_PROGRAM ": `%s': %s\n", path.c_str(), err.c_str());
+		return EXIT_FAILURE;
+	}
+	if (verbose > 0) fprintf(stderr, "Read %sB.\n", to_si((double)text.size()).c_str());
+	const std::string fmPath = toStdout ? "-" : path + ".fm";
+	fprintf(stderr, "Writing `%s'...\n", fmPath.c_str());
+	FILE* out = toStdout ? stdout : fopen(fmPath.c_str(), "wb");
+	if (!out) die_io(fmPath);
+	write_fm(out, sampleSA, sa, bwt);
+	if (fflush(out) != 0 || ferror(out)) die_io(fmPath);
+	if (!toStdout) fclose(out);
+	return EXIT_SUCCESS;
+}
+
+} // namespace abgmap

@@ -1,0 +1,55 @@
+// abyss-map -- drop-in for the reference's abyss-map (Map/map.cc), the stage abyss-pe runs once per library on the contigs:
+// the FM-index is built and every read is searched on the GPU through abg_fm_* (include/abyss_amd.h), everything else is
+// map_core.h.  No CPU fallback: without a HIP device the program fails.
+#include "map_core.h"
+
+#include "abyss_amd.h"
+
+#include <unistd.h>
+
+namespace {
+
+struct GpuBackend : abgmap::Backend {
+	abg_fm* f = nullptr;
+	~GpuBackend() override { if (f && getenv("ABG_ORDERLY_EXIT")) abg_fm_destroy(f); }
+	bool fail(std::string& err) { err = abg_fm_last_error(f); return false; }
+	bool build(const uint8_t* text, uint64_t n, std::string& err) override { return abg_fm_build(f, text, n) == ABG_OK || fail(err); }
+	bool exported(std::vector<uint32_t>& sa, std::vector<uint8_t>& bwt, std::string& err) override
+	{
+		uint64_t n = 0;
+		abg_fm_size(f, &n);
+		sa.resize(n + 1);
+		bwt.resize(n + 1);
+		return abg_fm_export(f, sa.data(), bwt.data()) == ABG_OK || fail(err);
+	}
+	bool map(const char* seqs, const uint64_t* off, uint64_t n, uint32_t k, uint32_t flags, abgmap::Hit* out, std::string& err) override
+	{
+		static_assert(sizeof(abgmap::Hit) == sizeof(abg_fm_hit), "one layout");
+		return abg_fm_map_seqs(f, seqs, off, n, k, flags, (abg_fm_hit*)out) == ABG_OK || fail(err);
+	}
+};
+
+abgmap::Backend* make_gpu(std::string& err)
+{
+	GpuBackend* b = new GpuBackend;
+	if (abg_fm_create(0, &b->f) != ABG_OK) {
+		err = abg_fm_last_error(nullptr);
+		delete b;
+		return nullptr;
+	}
+	return b;
+}
+
+} // namespace
+
+int main(int argc, char** argv)
+{
+#ifdef ABG_INDEX_MAIN
+	const int status = abgmap::index_main(argc, argv, make_gpu);
+#else
+	const int status = abgmap::map_main(argc, argv, make_gpu);
+#endif
+	fflush(NULL);
+	if (!getenv("ABG_ORDERLY_EXIT")) _exit(status); // (as the other drop-ins: the output is written; the kernel reclaims the device faster than we can)
+	return status;
+}

@@ -439,6 +439,39 @@ int abg_kn_sync(abg_kn* f); /* waits for everything queued */
 int abg_kn_profile(abg_kn* f, int on);
 int abg_kn_profile_get(abg_kn* f, const char* name, double* total_ms, uint64_t* launches);
 
+/* ---- the stage after rresolver: the FM-index of abyss-map and abyss-index (Map/map.cc, FMIndex/FMIndex.h) --------
+ * The text is a whole FASTA file, header lines included, upper-cased; alphabet "-ACGT" (codes 0..4), every other byte the
+ * sentinel and then 0 (FMIndex.h:186-187).  SA[0] = n, SA[1..n] the suffixes in lexicographic order, BWT[i] = text[SA[i] - 1].
+ * Positions are 32-bit on the device: abg_fm_build refuses a text of 2^32 - 1 bytes or more with ABG_EINVAL.  An abg_fm owns
+ * a HIP stream, the index in device memory (occurrence table and full suffix array) and its query buffers; one abg_fm is not
+ * thread-safe. */
+typedef struct abg_fm abg_fm;
+/* FMIndex::Match of one strand and SA[l] of a non-empty one (0xFFFFFFFF otherwise) */
+typedef struct abg_fm_hit { uint32_t l, u, qstart, qend, num, pos; } abg_fm_hit;
+#define ABG_FM_NO_RC 1u /* --no-rc: the reverse complement is not searched, its hit is all zero */
+#define ABG_FM_SS 2u    /* --SS: the reverse complement is searched with min_len, not with the forward match's span */
+int abg_fm_create(int device, abg_fm** out);
+void abg_fm_destroy(abg_fm* f);
+const char* abg_fm_last_error(const abg_fm* f); /* f may be NULL: the last failed abg_fm_create */
+/* FMIndex::assign over the raw bytes of the target file (buildFMIndex, map.cc:501-520); replaces an earlier index */
+int abg_fm_build(abg_fm* f, const uint8_t* text, uint64_t n);
+int abg_fm_size(const abg_fm* f, uint64_t* n); /* FMIndex::size(): the text's length, 0 before a build */
+/* the suffix array and the BWT (codes 0..4, 255 for the sentinel), n + 1 entries each; either may be NULL */
+int abg_fm_export(abg_fm* f, uint32_t* sa, uint8_t* bwt);
+/* findMatch (map.cc:325-341) of every sequence: out[2 * i] = FMIndex::find(seq, min_len), out[2 * i + 1] that of its reverse
+ * complement.  Sequences are ASCII with n + 1 offsets as in abg_load_seqs, case already folded (FastaReader::FOLD_CASE);
+ * a character outside the alphabet stops a search as in FMIndex::Translate.  The caller applies map.cc:363-383. */
+int abg_fm_map_seqs(abg_fm* f, const char* seqs, const uint64_t* offsets, uint64_t n, uint32_t min_len, uint32_t flags,
+    abg_fm_hit* out);
+int abg_fm_sync(abg_fm* f); /* waits for everything queued */
+/* The search runs CUs x waves_per_cu x 64 lanes, a read each (1..32; 0: the default, which notes/fm_map.md measured).  More waves
+ * hide more of the dependent gathers' latency and make the memo larger. */
+int abg_fm_tune(abg_fm* f, uint32_t waves_per_cu);
+/* kernel timing as abg_profile_enable / abg_profile_get: "fm_sa", "fm_occ", "fm_map"; "fm_map_steps" gives, as `launches`, the
+ * search steps (query characters taken, two table blocks each) of the abg_fm_map_seqs calls made while profiling */
+int abg_fm_profile(abg_fm* f, int on);
+int abg_fm_profile_get(abg_fm* f, const char* name, double* total_ms, uint64_t* launches);
+
 #ifdef __cplusplus
 }
 #endif
