@@ -66,6 +66,8 @@ def symbols():
         "abg_kn_contains_seqs", "abg_kn_popcount", "abg_kn_hash_seq", "abg_kn_sync", "abg_kn_profile", "abg_kn_profile_get",
         "abg_fm_create", "abg_fm_destroy", "abg_fm_last_error", "abg_fm_build", "abg_fm_size", "abg_fm_export", "abg_fm_map_seqs",
         "abg_fm_sync", "abg_fm_tune", "abg_fm_profile", "abg_fm_profile_get",
+        "abg_de_create", "abg_de_destroy", "abg_de_last_error", "abg_de_set_pmf", "abg_de_scan", "abg_de_estimate", "abg_de_tune",
+        "abg_de_profile", "abg_de_profile_get",
     ]
 
 
@@ -170,5 +172,16 @@ def load(path: str | None = None):
     lib.abg_fm_tune.argtypes = [vp, C.c_uint32]
     lib.abg_fm_profile.argtypes = [vp, C.c_int]
     lib.abg_fm_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
+    lib.abg_de_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.abg_de_destroy.argtypes = [vp]
+    lib.abg_de_destroy.restype = None
+    lib.abg_de_last_error.argtypes = [vp]
+    lib.abg_de_last_error.restype = C.c_char_p
+    lib.abg_de_set_pmf.argtypes = [vp, vp, C.c_uint64, C.c_double, C.c_double]
+    lib.abg_de_scan.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]
+    lib.abg_de_estimate.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp]
+    lib.abg_de_tune.argtypes = [vp, C.c_uint32]
+    lib.abg_de_profile.argtypes = [vp, C.c_int]
+    lib.abg_de_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
     _lib = lib
     return lib

@@ -679,3 +679,78 @@ class FMIndex:
         ms, n = C.c_double(), C.c_uint64()
         self._lib.abg_fm_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
         return ms.value, n.value
+
+
+DE_JOB = np.dtype([("first", "<i4"), ("last", "<i4"), ("len0", "<u4"), ("len1", "<u4")])
+DE_PAIR = np.dtype([("first", "<i4"), ("last", "<i4"), ("len0", "<u4"), ("len1", "<u4"), ("l", "<u4"), ("rf", "<u4")])
+
+
+class DistanceMLE:
+    """DistanceEst's maximum-likelihood estimate on one GPU (DistanceEst/MLE.cpp; include/abyss_amd.h abg_de_*): the scan over
+    theta on the device, every log and the O(thetas) tail on the host."""
+
+    def __init__(self, device: int = 0):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        rc = self._lib.abg_de_create(device, C.byref(self._h))
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_de_last_error(None)
+            self._h = None
+            raise AbyssAmdError("abg_de_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.abg_de_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_de_last_error(self._h)
+            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+
+    def set_pmf(self, pmf: np.ndarray, minp: float, mean: float) -> None:
+        """PMF(h): its values, minProbability() and mean()."""
+        p = np.ascontiguousarray(pmf, dtype=np.float64)
+        self._check(self._lib.abg_de_set_pmf(self._h, p.ctypes.data, len(p), minp, mean), "abg_de_set_pmf")
+
+    def scan(self, jobs: np.ndarray, values: np.ndarray, counts: np.ndarray, offsets: np.ndarray):
+        """(c, L, n) of every theta of every job (DE_JOB), job after job; job i's sample histogram is values / counts
+        [offsets[i], offsets[i + 1]) in ascending order of value."""
+        j = np.ascontiguousarray(jobs, dtype=DE_JOB)
+        v = np.ascontiguousarray(values, dtype=np.int32)
+        k = np.ascontiguousarray(counts, dtype=np.uint32)
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        total = int(sum(max(0, int(x["last"]) - int(x["first"]) + 1) for x in j))
+        c, like, n = np.zeros(total, dtype=np.float64), np.zeros(total, dtype=np.float64), np.zeros(total, dtype=np.uint32)
+        self._check(self._lib.abg_de_scan(self._h, j.ctypes.data, len(j), v.ctypes.data, k.ctypes.data, o.ctypes.data, c.ctypes.data,
+                                          like.ctypes.data, n.ctypes.data), "abg_de_scan")
+        return c, like, n
+
+    def estimate(self, pairs: np.ndarray, samples: np.ndarray, offsets: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """maximumLikelihoodEstimate of every pair (DE_PAIR): (distance, numPairs); pair i's samples are
+        samples[offsets[i], offsets[i + 1])."""
+        p = np.ascontiguousarray(pairs, dtype=DE_PAIR)
+        s = np.ascontiguousarray(samples, dtype=np.int32)
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        d, n = np.zeros(len(p), dtype=np.int32), np.zeros(len(p), dtype=np.uint32)
+        self._check(self._lib.abg_de_estimate(self._h, p.ctypes.data, len(p), s.ctypes.data, o.ctypes.data, d.ctypes.data, n.ctypes.data),
+                    "abg_de_estimate")
+        return d, n
+
+    def tune(self, block_threads: int) -> None:
+        """Thetas a workgroup: 64, 128, 192 or 256 (0 restores the default).  Changes no bit of any result."""
+        self._check(self._lib.abg_de_tune(self._h, block_threads), "abg_de_tune")
+
+    def profile(self, on: bool = True) -> None:
+        self._lib.abg_de_profile(self._h, int(on))
+
+    def profile_get(self, name: str) -> Tuple[float, int]:
+        ms, n = C.c_double(), C.c_uint64()
+        self._lib.abg_de_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
+        return ms.value, n.value

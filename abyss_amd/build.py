@@ -56,7 +56,11 @@ UNITS = {
     "abg_rr": ["abg_rr.hip", "abg_rr.h", "abg_core.h"],
     "abg_kn": ["abg_kn.hip", "abg_kn.h", "abg_core.h"],
     "abg_fm": ["abg_fm.hip", "abg_fm.h", "abg_core.h"],
+    "abg_de": ["abg_de.hip", "abg_de.h", "abg_core.h"],
 }
+# flags a unit adds to the common command line (abg_de: its sums must match a serial evaluation bit for bit, so no product may be
+# fused into an add, on the device or in the host tail)
+UNIT_FLAGS = {"abg_de": ["-ffp-contract=off"]}
 
 
 def build_lib(force: bool = False) -> str:
@@ -68,7 +72,8 @@ def build_lib(force: bool = False) -> str:
         obj = os.path.join(OBJ_DIR, unit + ".o")
         objs.append(obj)
         if force or _newer(obj, [os.path.join(CSRC, d) for d in deps] + [header]):
-            cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "-o", obj, os.path.join(CSRC, unit + ".hip")]
+            cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + UNIT_FLAGS.get(unit, []) + \
+                ["-c", "-o", obj, os.path.join(CSRC, unit + ".hip")]
             procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
     for cmd, p in procs:
         out, _ = p.communicate()
@@ -101,10 +106,11 @@ def build_cli(force: bool = False) -> str:
         _run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-o",
               os.path.join(BIN_DIR, "abyss-rresolver-short"), os.path.join(CSRC, "host", "rresolver_main.cc"),
               "-L" + os.path.dirname(LIB), "-labyss_amd", "-Wl,-rpath,$ORIGIN/../lib", "-lpthread"])
-        for name, main in (("abyss-map", "map_main.cc"), ("abyss-index", "index_main.cc")):
+        for name, main in (("abyss-map", "map_main.cc"), ("abyss-index", "index_main.cc"), ("DistanceEst", "distanceest_main.cc")):
             _run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-o",
                   os.path.join(BIN_DIR, name), os.path.join(CSRC, "host", main),
-                  "-L" + os.path.dirname(LIB), "-labyss_amd", "-Wl,-rpath,$ORIGIN/../lib", "-lpthread"])
+                  "-L" + os.path.dirname(LIB), "-labyss_amd", "-Wl,-rpath,$ORIGIN/../lib", "-lpthread"] +
+                 (["-ffp-contract=off"] if name == "DistanceEst" else []))
     return out
 
 
@@ -123,6 +129,7 @@ ADJLIST_CHECK = os.path.join(ROOT, "tests", "hostcheck", "adjlist_check")
 RRESOLVER_CHECK = os.path.join(ROOT, "tests", "hostcheck", "rresolver_check")
 KN_CHECK = os.path.join(ROOT, "tests", "hostcheck", "kn_check")
 FM_CHECK = os.path.join(ROOT, "tests", "hostcheck", "fm_check")
+DE_CHECK = os.path.join(ROOT, "tests", "hostcheck", "de_check")
 
 
 def build_hostcheck(force: bool = False) -> str:
@@ -152,6 +159,10 @@ def build_hostcheck(force: bool = False) -> str:
         [os.path.join(CSRC, "host", f) for f in ("map_core.h", "fasta_reader.h")]
     if force or _newer(FM_CHECK, fdeps):
         _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", FM_CHECK, fsrc, "-lpthread"])
+    dsrc = os.path.join(ROOT, "tests", "hostcheck", "de_check.cc")
+    ddeps = [dsrc] + [os.path.join(CSRC, f) for f in ("abg_de.h", "abg_core.h")] + [os.path.join(CSRC, "host", "distanceest_core.h")]
+    if force or _newer(DE_CHECK, ddeps):  # (no -march and no contraction: its sums are the reference's, bit for bit)
+        _run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wno-unknown-pragmas", "-o", DE_CHECK, dsrc, "-lpthread"])
     return HOSTCHECK
 
 

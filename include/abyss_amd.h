@@ -472,6 +472,46 @@ int abg_fm_tune(abg_fm* f, uint32_t waves_per_cu);
 int abg_fm_profile(abg_fm* f, int on);
 int abg_fm_profile_get(abg_fm* f, const char* name, double* total_ms, uint64_t* launches);
 
+/* ---- the stage after abyss-map: DistanceEst's maximum-likelihood estimate (DistanceEst/MLE.cpp, bin/abyss-pe:632-644) --------
+ * For every candidate distance theta of a contig pair the device computes
+ *   c(theta) = sum_{i=0..n-1} pmf[i] * window(i - theta)       window: MLE.cpp:26-33 with x1 = len0, x2 = len1, x3 = len0 + len1
+ *   L(theta) = sum over the sample histogram, ascending, of count * log(pmf[x + theta])
+ *   n(theta) = the samples with pmf[x + theta] > minp
+ * as IEEE double adds, multiplies and divides in the reference's order, so the arrays equal a serial host evaluation bit for bit.
+ * No log is taken on the device: the library makes log(pmf[i]) and log(minp) on the host when the PMF is set.  An index x + theta
+ * outside [0, n) reads minp (PMF::operator[]).  The O(thetas) tail (likelihood = L - nsamples * log(c), the Hann filter, the arg
+ * max) runs on at most 16 host threads while the device scans the next batch.  Work is batched by whole jobs up to
+ * ABG_DE_BATCH_THETAS thetas (environment, read by abg_de_create; default 2^20).  An abg_de owns a HIP stream, the PMF on the
+ * device and its batch buffers; one abg_de is not thread-safe. */
+typedef struct abg_de abg_de;
+/* thetas first..last (none if last < first) of a window with 0 < len0 <= len1: first/last after MLE.cpp:108-110, the lengths after
+ * the l - 1 correction and the swap of MLE.cpp:181-185 */
+typedef struct abg_de_job { int32_t first, last; uint32_t len0, len1; } abg_de_job;
+/* the arguments of maximumLikelihoodEstimate(l, first, last, samples, pmf, len0, len1, rf, n) (DistanceEst/MLE.h) */
+typedef struct abg_de_pair { int32_t first, last; uint32_t len0, len1, l, rf; } abg_de_pair;
+int abg_de_create(int device, abg_de** out);
+void abg_de_destroy(abg_de* d);
+const char* abg_de_last_error(const abg_de* d); /* d may be NULL: the last failed abg_de_create */
+/* PMF(h): pmf[0..n), PMF::minProbability() and PMF::mean(); replaces an earlier PMF.  The mean is the histogram's, which cannot be
+ * had back from pmf[] (empty bins hold minp); it sizes the Hann filter and the margin of first/last (MLE.cpp:108), so
+ * abg_de_estimate needs it and it is given here, once per PMF.  n, every theta and every sample value must lie within +-2^29. */
+int abg_de_set_pmf(abg_de* d, const double* pmf, uint64_t n, double minp, double mean);
+/* c, L and n of every theta of every job, job after job: sum of max(0, last - first + 1) entries each.  Job i's samples are
+ * sample_values / sample_counts [offsets[i], offsets[i + 1]): the histogram in ascending order of value. */
+int abg_de_scan(abg_de* d, const abg_de_job* jobs, uint64_t njobs, const int32_t* sample_values, const uint32_t* sample_counts,
+    const uint64_t* offsets, double* c, double* like, uint32_t* n);
+/* maximumLikelihoodEstimate of every pair: distance[i] its return value, num_pairs[i] its n.  Pair i's samples are
+ * samples[offsets[i], offsets[i + 1]), in any order.  Where the reference would fail an assertion (first >= last, no samples, a
+ * contig shorter than l, an FR sample of at most 2(l - 1)) the call returns ABG_EINVAL and abg_de_last_error says which pair. */
+int abg_de_estimate(abg_de* d, const abg_de_pair* pairs, uint64_t npairs, const int32_t* samples, const uint64_t* offsets,
+    int32_t* distance, uint32_t* num_pairs);
+/* thetas a workgroup: 64, 128, 192 or 256 (0: the default, 256).  Changes no bit of any result. */
+int abg_de_tune(abg_de* d, uint32_t block_threads);
+/* kernel timing as abg_profile_enable / abg_profile_get: "de_scan"; "de_scan_terms" gives, as `launches`, the terms (PMF entries x
+ * thetas) of the calls made while profiling */
+int abg_de_profile(abg_de* d, int on);
+int abg_de_profile_get(abg_de* d, const char* name, double* total_ms, uint64_t* launches);
+
 #ifdef __cplusplus
 }
 #endif
