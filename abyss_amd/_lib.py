@@ -68,6 +68,8 @@ def symbols():
         "abg_fm_sync", "abg_fm_tune", "abg_fm_profile", "abg_fm_profile_get",
         "abg_de_create", "abg_de_destroy", "abg_de_last_error", "abg_de_set_pmf", "abg_de_scan", "abg_de_estimate", "abg_de_tune",
         "abg_de_profile", "abg_de_profile_get",
+        "abg_ov_create", "abg_ov_destroy", "abg_ov_last_error", "abg_ov_set_contigs", "abg_ov_find", "abg_ov_profile",
+        "abg_ov_profile_get",
     ]
 
 
@@ -183,5 +185,14 @@ def load(path: str | None = None):
     lib.abg_de_tune.argtypes = [vp, C.c_uint32]
     lib.abg_de_profile.argtypes = [vp, C.c_int]
     lib.abg_de_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
+    lib.abg_ov_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.abg_ov_destroy.argtypes = [vp]
+    lib.abg_ov_destroy.restype = None
+    lib.abg_ov_last_error.argtypes = [vp]
+    lib.abg_ov_last_error.restype = C.c_char_p
+    lib.abg_ov_set_contigs.argtypes = [vp, vp, vp, C.c_uint64]
+    lib.abg_ov_find.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, vp, vp, C.POINTER(vp)]
+    lib.abg_ov_profile.argtypes = [vp, C.c_int]
+    lib.abg_ov_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
     _lib = lib
     return lib

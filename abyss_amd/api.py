@@ -754,3 +754,79 @@ class DistanceMLE:
         ms, n = C.c_double(), C.c_uint64()
         self._lib.abg_de_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
         return ms.value, n.value
+
+
+OV_PAIR = np.dtype([("t", "<u4"), ("h", "<u4")])
+
+
+class ContigOverlap:
+    """Overlap's suffix/prefix search on one GPU (Overlap/Overlap.cpp:151-198; include/abyss_amd.h abg_ov_*): for oriented contig
+    pairs (t, h), the lengths l for which the last l bytes of t are the first l bytes of h.  A node is 2 * id + sense; sense set
+    means the reverse complement."""
+
+    def __init__(self, device: int = 0):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        rc = self._lib.abg_ov_create(device, C.byref(self._h))
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_ov_last_error(None)
+            self._h = None
+            raise AbyssAmdError("abg_ov_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.abg_ov_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_ov_last_error(self._h)
+            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+
+    def set_contigs(self, seqs) -> None:
+        """The contigs, as bytes objects (or one uint8 array and its n + 1 offsets, as a tuple).  Case is folded to upper case here,
+        as the reference's reader does (FastaReader::FOLD_CASE)."""
+        if isinstance(seqs, tuple):
+            data = np.ascontiguousarray(seqs[0], dtype=np.uint8).copy()
+            off = np.ascontiguousarray(seqs[1], dtype=np.uint64)
+        else:
+            data = np.frombuffer(b"".join(seqs), dtype=np.uint8).copy()
+            off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+            np.cumsum([len(s) for s in seqs], out=off[1:])
+        lower = (data >= ord("a")) & (data <= ord("z"))
+        data[lower] -= 32
+        self._check(self._lib.abg_ov_set_contigs(self._h, data.ctypes.data, off.ctypes.data, len(off) - 1), "abg_ov_set_contigs")
+
+    def find(self, pairs: np.ndarray, all: bool = False):
+        """all=False: (top, n), top[i] the three largest matching lengths of pair i (zero-filled, uint32 [npairs, 3]) and n[i] how
+        many of them exist.  all=True: (lengths, offsets), every matching length of pair i, descending, at
+        lengths[offsets[i]:offsets[i + 1]].  `pairs` is OV_PAIR, or anything of shape [npairs, 2]."""
+        p = np.asarray(pairs)
+        if p.dtype != OV_PAIR:
+            p = np.ascontiguousarray(p, dtype=np.uint32).reshape(-1, 2)
+        p = np.ascontiguousarray(p)
+        n = len(p)
+        if not all:
+            top, cnt = np.zeros((n, 3), dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+            self._check(self._lib.abg_ov_find(self._h, p.ctypes.data, n, 0, top.ctypes.data, cnt.ctypes.data, None, None), "abg_ov_find")
+            return top, cnt
+        off = np.zeros(n + 1, dtype=np.uint64)
+        ptr = C.c_void_p()
+        self._check(self._lib.abg_ov_find(self._h, p.ctypes.data, n, 1, None, None, off.ctypes.data, C.byref(ptr)), "abg_ov_find")
+        total = int(off[n])
+        lengths = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint32)), shape=(total,)).copy() if total else np.zeros(0, dtype=np.uint32)
+        return lengths, off
+
+    def profile(self, on: bool = True) -> None:
+        self._lib.abg_ov_profile(self._h, int(on))
+
+    def profile_get(self, name: str) -> Tuple[float, int]:
+        ms, n = C.c_double(), C.c_uint64()
+        self._lib.abg_ov_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
+        return ms.value, n.value

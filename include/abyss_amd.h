@@ -512,6 +512,39 @@ int abg_de_tune(abg_de* d, uint32_t block_threads);
 int abg_de_profile(abg_de* d, int on);
 int abg_de_profile_get(abg_de* d, const char* name, double* total_ms, uint64_t* launches);
 
+/* ---- the stage after DistanceEst: Overlap's suffix/prefix search (Overlap/Overlap.cpp, bin/abyss-pe:658-659) -------------------
+ * findOverlap (Overlap.cpp:151-198) asks, for a tail node t and a head node h, which lengths l = min(|t|, |h|) .. 1 make the last
+ * l bytes of sequence(t) the first l bytes of sequence(h).  The device answers that for many pairs at once, a wavefront a pair,
+ * 64 lengths a step, comparing bytes as they are: N and the IUPAC codes equal only themselves, as std::string's == has it.
+ * Everything that decides what to do with the answer stays with the caller.  Pairs are searched longest first, in launches of at
+ * most ABG_OV_BATCH_PAIRS pairs (environment, read by abg_ov_create; default 2^20); the results come back in the caller's order.
+ * An abg_ov owns a HIP stream, the contigs on the device and its batch buffers; one abg_ov is not thread-safe. */
+typedef struct abg_ov abg_ov;
+/* an oriented pair: ContigNode indices, 2 * id + sense (Common/ContigNode.h:84-88); sense set means the reverse complement
+ * (Overlap.cpp:145-149) */
+typedef struct abg_ov_pair { uint32_t t, h; } abg_ov_pair;
+enum { ABG_OV_TOP = 0, ABG_OV_ALL = 1 };
+int abg_ov_create(int device, abg_ov** out);
+void abg_ov_destroy(abg_ov* o);
+const char* abg_ov_last_error(const abg_ov* o); /* o may be NULL: the last failed abg_ov_create */
+/* g_contigs (Overlap.cpp:355-363): contig i is bytes[offsets[i], offsets[i + 1]), offsets[0] = 0, case already folded as
+ * FastaReader::FOLD_CASE does.  The device writes every reverse complement beside it (Common/Sequence.cpp:50-58).  A byte on which
+ * complementBaseChar asserts (Sequence.cpp:41-44) is refused with ABG_EINVAL before anything is uploaded, and abg_ov_last_error
+ * names the contig and the position.  Replaces earlier contigs.  A contig has at most 2^32 - 1 bytes. */
+int abg_ov_set_contigs(abg_ov* o, const uint8_t* bytes, const uint64_t* offsets, uint64_t n);
+/* The loop of Overlap.cpp:159-166 for every pair.
+ * ABG_OV_TOP: top3[3 i .. 3 i + 2] the three largest matching lengths of pair i, zero-filled, ntop[i] how many of them exist
+ *   (0..3): all that Overlap.cpp:177-197 reads.  The search of a pair stops at its third match.  all_offsets and all may be NULL.
+ * ABG_OV_ALL: every matching length of pair i, descending, at (*all)[all_offsets[i] .. all_offsets[i + 1]): the `overlaps` vector
+ *   that -v prints (Overlap.cpp:168-175).  all_offsets has npairs + 1 entries; *all belongs to the abg_ov and holds until its next
+ *   call.  top3 and ntop may be NULL. */
+int abg_ov_find(abg_ov* o, const abg_ov_pair* pairs, uint64_t npairs, int mode, uint32_t* top3, uint32_t* ntop, uint64_t* all_offsets,
+    const uint32_t** all);
+/* kernel timing as abg_profile_enable / abg_profile_get: "ov_rc", "ov_search"; "ov_search_bytes" gives, as `launches`, the bytes
+ * a search must read at least (2 min(|t|, |h|) a pair) of the calls made while profiling */
+int abg_ov_profile(abg_ov* o, int on);
+int abg_ov_profile_get(abg_ov* o, const char* name, double* total_ms, uint64_t* launches);
+
 #ifdef __cplusplus
 }
 #endif
