@@ -70,6 +70,8 @@ def symbols():
         "abg_de_profile", "abg_de_profile_get",
         "abg_ov_create", "abg_ov_destroy", "abg_ov_last_error", "abg_ov_set_contigs", "abg_ov_find", "abg_ov_profile",
         "abg_ov_profile_get",
+        "abg_sg_create", "abg_sg_destroy", "abg_sg_last_error", "abg_sg_set_graph", "abg_sg_search", "abg_sg_tune", "abg_sg_profile",
+        "abg_sg_profile_get",
     ]
 
 
@@ -194,5 +196,15 @@ def load(path: str | None = None):
     lib.abg_ov_find.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, vp, vp, C.POINTER(vp)]
     lib.abg_ov_profile.argtypes = [vp, C.c_int]
     lib.abg_ov_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
+    lib.abg_sg_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.abg_sg_destroy.argtypes = [vp]
+    lib.abg_sg_destroy.restype = None
+    lib.abg_sg_last_error.argtypes = [vp]
+    lib.abg_sg_last_error.restype = C.c_char_p
+    lib.abg_sg_set_graph.argtypes = [vp, C.c_uint64, vp, vp, vp, vp]
+    lib.abg_sg_search.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]
+    lib.abg_sg_tune.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]
+    lib.abg_sg_profile.argtypes = [vp, C.c_int]
+    lib.abg_sg_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
     _lib = lib
     return lib

@@ -830,3 +830,80 @@ class ContigOverlap:
         ms, n = C.c_double(), C.c_uint64()
         self._lib.abg_ov_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
         return ms.value, n.value
+
+
+class PathSearch:
+    """SimpleGraph's constrained path search on one GPU (Graph/ConstrainedSearch.h:56-144; include/abyss_amd.h abg_sg_*): from an
+    oriented vertex, every path through the graph on which each constraint vertex lies within its bound, in the order the reference's
+    depth-first search finds them.  A vertex is 2 * id + sense."""
+
+    def __init__(self, device: int = 0):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        rc = self._lib.abg_sg_create(device, C.byref(self._h))
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_sg_last_error(None)
+            self._h = None
+            raise AbyssAmdError("abg_sg_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.abg_sg_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_sg_last_error(self._h)
+            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+
+    def set_graph(self, edge_offsets, lengths, targets, distances) -> None:
+        """The graph in CSR form: vertex u has length lengths[u] and the out-edges edge_offsets[u]:edge_offsets[u + 1] of targets and
+        distances, in the order the search is to try them."""
+        off = np.ascontiguousarray(edge_offsets, dtype=np.uint64)
+        length = np.ascontiguousarray(lengths, dtype=np.uint32)
+        tgt = np.ascontiguousarray(targets, dtype=np.uint32)
+        dist = np.ascontiguousarray(distances, dtype=np.int32)
+        if len(off) != len(length) + 1 or len(tgt) != len(dist) or (len(off) and int(off[-1]) != len(tgt)):
+            raise AbyssAmdError("set_graph: edge_offsets needs len(lengths) + 1 entries and must end at len(targets) == len(distances)")
+        self._check(self._lib.abg_sg_set_graph(self._h, len(length), off.ctypes.data, length.ctypes.data, tgt.ctypes.data, dist.ctypes.data), "abg_sg_set_graph")
+
+    def search(self, searches, max_cost: int = 100000, max_paths: int = 200):
+        """searches: [(origin, [(vertex, bound), ...]), ...].  Returns (visited, redone, paths): visited[i] the reference's numVisited,
+        redone[i] whether the host ran search i again because it outgrew a limit of the kernel, paths[i] its paths in discovery order
+        (lists of vertices, the origin not included; at most max_paths + 1 of them)."""
+        n = len(searches)
+        origins = np.array([o for o, _ in searches], dtype=np.uint32)
+        coff = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum([len(c) for _, c in searches], out=coff[1:])
+        cv = np.array([v for _, c in searches for v, _ in c], dtype=np.uint32)
+        cb = np.array([b for _, c in searches for _, b in c], dtype=np.int32)
+        visited, redone = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8)
+        index = np.zeros(n + 1, dtype=np.uint64)
+        poff, nodes = C.c_void_p(), C.c_void_p()
+        self._check(self._lib.abg_sg_search(self._h, n, origins.ctypes.data, coff.ctypes.data, cv.ctypes.data, cb.ctypes.data, max_cost, max_paths,
+                                            visited.ctypes.data, redone.ctypes.data, index.ctypes.data, C.byref(poff), C.byref(nodes)), "abg_sg_search")
+        npaths = int(index[n])
+        off = np.ctypeslib.as_array(C.cast(poff, C.POINTER(C.c_uint64)), shape=(npaths + 1,)).copy()
+        total = int(off[npaths])
+        flat = np.ctypeslib.as_array(C.cast(nodes, C.POINTER(C.c_uint32)), shape=(total,)).copy() if total else np.zeros(0, dtype=np.uint32)
+        paths = [[flat[int(off[p]):int(off[p + 1])].tolist() for p in range(int(index[i]), int(index[i + 1]))] for i in range(n)]
+        return visited, redone.astype(bool), paths
+
+    def tune(self, stack_depth: int = 0, max_constraints: int = 0, arena_words: int = 0, lanes: int = 0) -> None:
+        self._check(self._lib.abg_sg_tune(self._h, stack_depth, max_constraints, arena_words, lanes), "abg_sg_tune")
+
+    def profile(self, on: bool = True, count_steps: bool = False) -> None:
+        """on: time the launches ("sg_search").  count_steps: the kernel also counts its wave steps ("sg_steps", "sg_thin_steps"),
+        which slows it, so time without."""
+        self._lib.abg_sg_profile(self._h, (2 if count_steps else 1) if on else 0)
+
+    def profile_get(self, name: str) -> Tuple[float, int]:
+        ms, n = C.c_double(), C.c_uint64()
+        self._lib.abg_sg_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
+        return ms.value, n.value

@@ -58,6 +58,7 @@ UNITS = {
     "abg_fm": ["abg_fm.hip", "abg_fm.h", "abg_core.h"],
     "abg_de": ["abg_de.hip", "abg_de.h", "abg_core.h"],
     "abg_ov": ["abg_ov.hip", "abg_ov.h", "abg_core.h"],
+    "abg_sg": ["abg_sg.hip", "abg_sg.h", "abg_core.h"],
 }
 # flags a unit adds to the common command line (abg_de: its sums must match a serial evaluation bit for bit, so no product may be
 # fused into an add, on the device or in the host tail)
@@ -108,7 +109,7 @@ def build_cli(force: bool = False) -> str:
               os.path.join(BIN_DIR, "abyss-rresolver-short"), os.path.join(CSRC, "host", "rresolver_main.cc"),
               "-L" + os.path.dirname(LIB), "-labyss_amd", "-Wl,-rpath,$ORIGIN/../lib", "-lpthread"])
         for name, main in (("abyss-map", "map_main.cc"), ("abyss-index", "index_main.cc"), ("DistanceEst", "distanceest_main.cc"),
-                           ("Overlap", "overlap_main.cc")):
+                           ("Overlap", "overlap_main.cc"), ("SimpleGraph", "simplegraph_main.cc")):
             _run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-o",
                   os.path.join(BIN_DIR, name), os.path.join(CSRC, "host", main),
                   "-L" + os.path.dirname(LIB), "-labyss_amd", "-Wl,-rpath,$ORIGIN/../lib", "-lpthread"] +
@@ -133,6 +134,7 @@ KN_CHECK = os.path.join(ROOT, "tests", "hostcheck", "kn_check")
 FM_CHECK = os.path.join(ROOT, "tests", "hostcheck", "fm_check")
 DE_CHECK = os.path.join(ROOT, "tests", "hostcheck", "de_check")
 OV_CHECK = os.path.join(ROOT, "tests", "hostcheck", "ov_check")
+SG_CHECK = os.path.join(ROOT, "tests", "hostcheck", "sg_check")
 
 
 def build_hostcheck(force: bool = False) -> str:
@@ -171,6 +173,11 @@ def build_hostcheck(force: bool = False) -> str:
         [os.path.join(CSRC, "host", f) for f in ("overlap_core.h", "rresolver_core.h", "graph_writers.h", "fasta_reader.h", "si_bytes.h")]
     if force or _newer(OV_CHECK, odeps):
         _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", OV_CHECK, osrc, "-lpthread"])
+    ssrc = os.path.join(ROOT, "tests", "hostcheck", "sg_check.cc")
+    sdeps = [ssrc] + [os.path.join(CSRC, f) for f in ("abg_sg.h", "abg_core.h")] + \
+        [os.path.join(CSRC, "host", f) for f in ("simplegraph_core.h", "overlap_core.h", "rresolver_core.h", "graph_writers.h", "fasta_reader.h", "si_bytes.h")]
+    if force or _newer(SG_CHECK, sdeps):
+        _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", SG_CHECK, ssrc, "-lpthread"])
     return HOSTCHECK
 
 

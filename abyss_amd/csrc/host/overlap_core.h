@@ -204,6 +204,52 @@ struct Stats { unsigned overlap = 0, scaffold = 0, none = 0, tooshort = 0, homop
 // one estimate as the reference meets it
 struct DistCall { unsigned ref; bool rc; V pair; Est est; };
 
+// operator>>(istream&, EstimateRecord&), Estimate.h:171-196, over a whole .dist file (SimpleGraph reads the same records):
+// record(ref) for every record, then estimate(ref, rc, vertex, distance, numPairs, stdDev) for each of its estimates in file order.
+// A name the graph lacks ends the run as Graph::find_contig does; `bad` is given the message for a malformed estimate.
+template <class Record, class Estimate, class Bad>
+inline void read_dist_records(const std::string& text, const abgrr::Graph& graph, const std::string& path, Record record, Estimate estimate, Bad bad)
+{
+	size_t p = 0;
+	auto skip = [&]() { while (p < text.size() && isspace((unsigned char)text[p])) p++; };
+	for (;;) {
+		skip();
+		if (p >= text.size()) break;
+		size_t e = p;
+		while (e < text.size() && !isspace((unsigned char)text[e])) e++;
+		const unsigned ref = graph.find_contig(text.substr(p, e - p));
+		record(ref);
+		p = e;
+		for (int rc = 0; rc <= 1; ++rc) {
+			size_t end = text.find(rc ? '\n' : ';', p);
+			if (end == std::string::npos) end = text.size();
+			const std::string part = text.substr(p, end - p);
+			p = std::min(text.size(), end + 1);
+			size_t q = 0;
+			for (;;) {
+				while (q < part.size() && isspace((unsigned char)part[q])) q++;
+				if (q >= part.size()) break;
+				size_t comma = part.find(',', q);
+				if (comma == std::string::npos) comma = part.size();
+				const V v = graph.find_vertex(part.substr(q, comma - q));
+				q = std::min(part.size(), comma + 1);
+				// distance,numPairs,stdDev
+				char* end1 = nullptr;
+				const char* b = part.c_str() + q;
+				const int distance = (int)strtol(b, &end1, 10);
+				unsigned numPairs = 0;
+				float stdDev = 0;
+				bool ok = end1 != b && *end1 == ',';
+				if (ok) { b = end1 + 1; numPairs = (unsigned)strtoul(b, &end1, 10); ok = end1 != b && *end1 == ','; }
+				if (ok) { b = end1 + 1; stdDev = strtof(b, &end1); ok = end1 != b; }
+				if (!ok) bad("`" + path + "': malformed estimate near `" + part.substr(q, 30) + "'");
+				q = (size_t)(end1 - part.c_str());
+				estimate(ref, rc != 0, v, distance, numPairs, stdDev);
+			}
+		}
+	}
+}
+
 class Run {
   public:
 	Run(Options& o, Searcher& s) : opt(o), searcher(s), scaffoldGraph(0) {}
@@ -357,47 +403,21 @@ class Run {
 	// operator<<(ostream&, const Overlap&), Overlap.cpp:232-236
 	static std::string show(const Est& o) { return "d=" + std::to_string(o.overlap > 0 ? -(int)o.overlap : o.distance); }
 
-	// operator>>(istream&, EstimateRecord&), Estimate.h:171-196: every estimate of the file in the order main meets them
+	// every estimate of the file in the order main meets them
 	void read_dist(const std::string& text, std::vector<DistCall>& calls)
 	{
-		size_t p = 0;
-		auto skip = [&]() { while (p < text.size() && isspace((unsigned char)text[p])) p++; };
-		for (;;) {
-			skip();
-			if (p >= text.size()) break;
-			size_t e = p;
-			while (e < text.size() && !isspace((unsigned char)text[e])) e++;
-			const unsigned ref = graph.find_contig(text.substr(p, e - p));
-			p = e;
-			for (int rc = 0; rc <= 1; ++rc) {
-				size_t end = text.find(rc ? '\n' : ';', p);
-				if (end == std::string::npos) end = text.size();
-				const std::string part = text.substr(p, end - p);
-				p = std::min(text.size(), end + 1);
-				size_t q = 0;
-				for (;;) {
-					while (q < part.size() && isspace((unsigned char)part[q])) q++;
-					if (q >= part.size()) break;
-					size_t comma = part.find(',', q);
-					if (comma == std::string::npos) comma = part.size();
-					DistCall c;
-					c.ref = ref;
-					c.rc = rc != 0;
-					c.pair = graph.find_vertex(part.substr(q, comma - q));
-					q = std::min(part.size(), comma + 1);
-					// distance,numPairs,stdDev
-					char* end1 = nullptr;
-					const char* b = part.c_str() + q;
-					c.est.distance = (int)strtol(b, &end1, 10);
-					bool ok = end1 != b && *end1 == ',';
-					if (ok) { b = end1 + 1; c.est.numPairs = (unsigned)strtoul(b, &end1, 10); ok = end1 != b && *end1 == ','; }
-					if (ok) { b = end1 + 1; c.est.stdDev = strtof(b, &end1); ok = end1 != b; }
-					if (!ok) fail("`" + opt.estPath + "': malformed estimate near `" + part.substr(q, 30) + "'");
-					q = (size_t)(end1 - part.c_str());
-					calls.push_back(c);
-				}
-			}
-		}
+		read_dist_records(text, graph, opt.estPath, [](unsigned) {},
+		    [&](unsigned ref, bool rc, V v, int distance, unsigned numPairs, float stdDev) {
+			    DistCall c;
+			    c.ref = ref;
+			    c.rc = rc;
+			    c.pair = v;
+			    c.est.distance = distance;
+			    c.est.numPairs = numPairs;
+			    c.est.stdDev = stdDev;
+			    calls.push_back(c);
+		    },
+		    [](const std::string& msg) { fail(msg); });
 	}
 
 	// the answer for (t, h): overlaps, descending (the first three at least)

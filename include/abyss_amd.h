@@ -545,6 +545,50 @@ int abg_ov_find(abg_ov* o, const abg_ov_pair* pairs, uint64_t npairs, int mode, 
 int abg_ov_profile(abg_ov* o, int on);
 int abg_ov_profile_get(abg_ov* o, const char* name, double* total_ms, uint64_t* launches);
 
+/* ---- the stage after Overlap: SimpleGraph's constrained path search (SimpleGraph/SimpleGraph.cpp, bin/abyss-pe:663-664) ---------
+ * constrainedSearch (Graph/ConstrainedSearch.h:56-144) walks the overlap graph depth first from one contig end and keeps every path
+ * on which each constraint vertex lies within its bound.  The device runs many such searches at once, a lane a search; within a
+ * search the order is the reference's, so the visit count and the paths, in discovery order, are the reference's.  A search stops
+ * when its visit count reaches max_cost or when it has recorded max_paths + 1 paths (the caller tests visited >= max_cost and
+ * paths > max_paths, SimpleGraph.cpp:493-494).  Everything that judges the paths stays with the caller.
+ * The kernel has fixed limits: frames a search (ABG_SG_STACK_DEPTH, default 512), constraints a search (ABG_SG_MAX_CONSTRAINTS,
+ * default and most 64) and the words of paths a launch holds (ABG_SG_ARENA_WORDS, default 2^24); searches go out in launches of at
+ * most ABG_SG_BATCH (default 2^20) on at most ABG_SG_LANES lanes (default 32768, rounded up to whole waves; with fewer lanes than
+ * searches a lane takes the next search when its own ends).  All five are read from the environment by abg_sg_create.  Searches that
+ * find the arena full are launched again, fewer at a time.  A search that exceeds the stack depth or the constraint limit, or
+ * fills the arena on its own, is run again on the host by the same code and reported as redone: no limit changes a result.
+ * A launch allocates lanes x stack depth x 16 bytes of frames (256 MiB at the defaults once a call has 32,768 searches or more)
+ * and 4 bytes an arena word (64 MiB): raising ABG_SG_LANES or ABG_SG_STACK_DEPTH raises that product, and the largest values
+ * abg_sg_tune takes multiply to 2^40 bytes, which no device holds (the call then fails with ABG_ENOMEM).
+ * An abg_sg owns a HIP stream, the graph on the device and its buffers; one abg_sg is not thread-safe. */
+typedef struct abg_sg abg_sg;
+int abg_sg_create(int device, abg_sg** out);
+void abg_sg_destroy(abg_sg* s);
+const char* abg_sg_last_error(const abg_sg* s); /* s may be NULL: the last failed abg_sg_create */
+/* The graph in CSR form over oriented vertices (ContigNode indices, 2 * id + sense): vertex u has length lengths[u] and the
+ * out-edges edge_offsets[u] .. edge_offsets[u + 1], each a target and a distance, in the order the reference's reader adds them
+ * (Graph/AdjIO.h, Graph/DotIO.h), which is the order the search tries them in.  Replaces an earlier graph. */
+int abg_sg_set_graph(abg_sg* s, uint64_t nv, const uint64_t* edge_offsets, const uint32_t* lengths, const uint32_t* targets,
+    const int32_t* distances);
+/* Search i starts at origins[i] under the constraints constraint_offsets[i] .. constraint_offsets[i + 1], each a vertex and the
+ * largest distance it may lie at, in any order (they are sorted here as ConstrainedSearch.h:134 sorts them).  A search with no
+ * constraint finds nothing (ConstrainedSearch.h:130-131).
+ * visited[i]: the reference's numVisited.  redone[i]: 1 where the host ran the search again.  The paths of search i are the paths
+ * path_index[i] .. path_index[i + 1] (path_index has nsearch + 1 entries), and path p is (*path_nodes)[(*path_offsets)[p] ..
+ * (*path_offsets)[p + 1]], the origin not included.  *path_offsets and *path_nodes belong to the abg_sg and hold until its next
+ * call. */
+int abg_sg_search(abg_sg* s, uint64_t nsearch, const uint32_t* origins, const uint64_t* constraint_offsets, const uint32_t* constraint_vertices,
+    const int32_t* constraint_bounds, uint32_t max_cost, uint32_t max_paths, uint32_t* visited, uint8_t* redone, uint64_t* path_index,
+    const uint64_t** path_offsets, const uint32_t** path_nodes);
+/* the limits above and the most lanes a launch uses (default 32768); 0 keeps a value.  Changes no result. */
+int abg_sg_tune(abg_sg* s, uint32_t stack_depth, uint32_t max_constraints, uint64_t arena_words, uint32_t lanes);
+/* kernel timing as abg_profile_enable / abg_profile_get: "sg_search" (on = 1: events around the launches, the kernel as every run
+ * has it).  on = 2 makes the kernel also count, which costs it two ballots a step: as `launches`, "sg_steps" the steps the waves
+ * took and "sg_thin_steps" those taken with fewer than half of a wave's lanes holding a search.  "sg_redone": the searches run again
+ * on the host, in every mode. */
+int abg_sg_profile(abg_sg* s, int on);
+int abg_sg_profile_get(abg_sg* s, const char* name, double* total_ms, uint64_t* launches);
+
 #ifdef __cplusplus
 }
 #endif
