@@ -72,6 +72,8 @@ def symbols():
         "abg_ov_profile_get",
         "abg_sg_create", "abg_sg_destroy", "abg_sg_last_error", "abg_sg_set_graph", "abg_sg_search", "abg_sg_tune", "abg_sg_profile",
         "abg_sg_profile_get",
+        "abg_mc_create", "abg_mc_destroy", "abg_mc_last_error", "abg_mc_set_contigs", "abg_mc_merge", "abg_mc_tune", "abg_mc_profile",
+        "abg_mc_profile_get",
     ]
 
 
@@ -206,5 +208,15 @@ def load(path: str | None = None):
     lib.abg_sg_tune.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]
     lib.abg_sg_profile.argtypes = [vp, C.c_int]
     lib.abg_sg_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
+    lib.abg_mc_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.abg_mc_destroy.argtypes = [vp]
+    lib.abg_mc_destroy.restype = None
+    lib.abg_mc_last_error.argtypes = [vp]
+    lib.abg_mc_last_error.restype = C.c_char_p
+    lib.abg_mc_set_contigs.argtypes = [vp, vp, vp, C.c_uint64]
+    lib.abg_mc_merge.argtypes = [vp, C.c_uint32, C.c_uint64, vp, vp, vp, C.c_int, vp, vp, C.POINTER(vp), vp, vp, C.POINTER(vp)]
+    lib.abg_mc_tune.argtypes = [vp, C.c_uint64, C.c_uint64]
+    lib.abg_mc_profile.argtypes = [vp, C.c_int]
+    lib.abg_mc_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
     _lib = lib
     return lib

@@ -907,3 +907,73 @@ class PathSearch:
         ms, n = C.c_double(), C.c_uint64()
         self._lib.abg_sg_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
         return ms.value, n.value
+
+
+class PathMerge:
+    """MergeContigs' sequence merge on one GPU (MergePaths/MergeContigs.cpp:159-313; include/abyss_amd.h abg_mc_*): paths of contigs
+    spliced at their overlaps.  A node is 2 * id + sense, or -n for the gap of n bases."""
+
+    def __init__(self, device: int = 0):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        rc = self._lib.abg_mc_create(device, C.byref(self._h))
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_mc_last_error(None)
+            self._h = None
+            raise AbyssAmdError("abg_mc_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.abg_mc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_mc_last_error(self._h)
+            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+
+    def set_contigs(self, contigs) -> None:
+        """contigs: the sequences as bytes, case and IUPAC codes as they are to stay"""
+        off = np.zeros(len(contigs) + 1, dtype=np.uint64)
+        np.cumsum([len(c) for c in contigs], out=off[1:])
+        data = np.frombuffer(b"".join(contigs), dtype=np.uint8) if len(contigs) and int(off[-1]) else np.zeros(1, dtype=np.uint8)
+        self._check(self._lib.abg_mc_set_contigs(self._h, data.ctypes.data, off.ctypes.data, len(contigs)), "abg_mc_set_contigs")
+
+    def merge(self, k: int, paths, verbose: int = 0):
+        """paths: [(nodes, overlaps), ...], overlaps[j] the overlap of nodes[j] with what precedes it (overlaps[0] is not read).
+        Returns (sequences, acgt, redone, logs): the merged sequences as bytes, their counts of A, C, G and T, whether the host merged
+        path i because a junction had no consensus, and what the reference writes to stderr for it, names as placeholders."""
+        n = len(paths)
+        noff = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum([len(p[0]) for p in paths], out=noff[1:])
+        nodes = np.array([u for p in paths for u in p[0]], dtype=np.int32)
+        ov = np.array([o for p in paths for o in p[1]], dtype=np.uint32)
+        if len(nodes) != len(ov):
+            raise AbyssAmdError("merge: a path needs as many overlaps as nodes")
+        redone, acgt = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint64)
+        soff, loff = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+        seqs, logs = C.c_void_p(), C.c_void_p()
+        self._check(self._lib.abg_mc_merge(self._h, k, n, noff.ctypes.data, nodes.ctypes.data, ov.ctypes.data, verbose, redone.ctypes.data, soff.ctypes.data,
+                                           C.byref(seqs), acgt.ctypes.data, loff.ctypes.data, C.byref(logs)), "abg_mc_merge")
+        flat = C.string_at(seqs, int(soff[n])) if int(soff[n]) else b""
+        text = C.string_at(logs, int(loff[n])) if int(loff[n]) else b""
+        return ([flat[int(soff[i]):int(soff[i + 1])] for i in range(n)], acgt, redone.astype(bool),
+                [text[int(loff[i]):int(loff[i + 1])].decode() for i in range(n)])
+
+    def tune(self, tile: int = 0, batch: int = 0) -> None:
+        """bytes a splice tile (a multiple of 16) and paths a launch; 0 keeps a value"""
+        self._check(self._lib.abg_mc_tune(self._h, tile, batch), "abg_mc_tune")
+
+    def profile(self, on: bool = True) -> None:
+        self._lib.abg_mc_profile(self._h, 1 if on else 0)
+
+    def profile_get(self, name: str) -> Tuple[float, int]:
+        ms, n = C.c_double(), C.c_uint64()
+        self._lib.abg_mc_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
+        return ms.value, n.value

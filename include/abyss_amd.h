@@ -589,6 +589,38 @@ int abg_sg_tune(abg_sg* s, uint32_t stack_depth, uint32_t max_constraints, uint6
 int abg_sg_profile(abg_sg* s, int on);
 int abg_sg_profile_get(abg_sg* s, const char* name, double* total_ms, uint64_t* launches);
 
+/* ---- MergeContigs: paths of contigs spliced into sequences (MergePaths/MergeContigs.cpp:159-313) ----------------------------------
+ * A node is 2 * contig + sense, or -n for the gap of n bases (k - 1 'N', then n 'N', lowercase when n < k).  A path's sequence is
+ * its first node's, and for every further node the consensus of the last `overlap` characters so far with the node's first
+ * `overlap` (createConsensus: equal characters, N gives way, an IUPAC code joins a subset of it, lowercase wins) followed by the
+ * rest of the node.  Two kernels do this for every path of a call: one walks each path's junctions and writes their consensus, one
+ * writes the output bytes flat, in tiles of ABG_MC_TILE bytes (default 16384, a multiple of 16), and counts each output's ACGT.
+ * Paths go out ABG_MC_BATCH at a time (default 2^20).  Both are read from the environment by abg_mc_create and change no result.
+ * A path with a junction that has no consensus (or an overlap of more than 1024) is merged again on the host by the same header's
+ * serial text -- the chomp retry, the overlap alignment, the warning -- and reported as redone.
+ * An abg_mc owns a HIP stream, the contigs on the device and its buffers; one abg_mc is not thread-safe. */
+typedef struct abg_mc abg_mc;
+int abg_mc_create(int device, abg_mc** out);
+void abg_mc_destroy(abg_mc* s);
+const char* abg_mc_last_error(const abg_mc* s); /* s may be NULL: the last failed abg_mc_create */
+/* The contigs' bytes end to end as the file has them (case and IUPAC codes kept), contig i at offsets[i] .. offsets[i + 1].
+ * Replaces earlier contigs. */
+int abg_mc_set_contigs(abg_mc* s, const uint8_t* bytes, const uint64_t* offsets, uint64_t n);
+/* Path i is nodes[node_offsets[i] .. node_offsets[i + 1]]; overlaps[j] is the overlap of nodes[j] with what precedes it (ignored
+ * for a path's first node, positive elsewhere).  The sequence of path i is (*seqs)[seq_offsets[i] .. seq_offsets[i + 1]], acgt[i]
+ * counts its A, C, G and T of either case, redone[i] is 1 where the host merged it.  What the reference writes to stderr while it
+ * merges a redone path (the -vvv alignment at verbose > 2, the warning block) is (*logs)[log_offsets[i] .. log_offsets[i + 1]], with
+ * "\x01" j "\x02" for the name of the path's node j and "\x03" for the path as printed, which the caller substitutes.
+ * seq_offsets and log_offsets have npaths + 1 entries; *seqs and *logs belong to the abg_mc and hold until its next call. */
+int abg_mc_merge(abg_mc* s, uint32_t k, uint64_t npaths, const uint64_t* node_offsets, const int32_t* nodes, const uint32_t* overlaps, int verbose,
+    uint8_t* redone, uint64_t* seq_offsets, const uint8_t** seqs, uint64_t* acgt, uint64_t* log_offsets, const char** logs);
+/* bytes a splice tile (a multiple of 16) and paths a launch; 0 keeps a value.  Changes no result. */
+int abg_mc_tune(abg_mc* s, uint64_t tile, uint64_t batch);
+/* kernel timing as abg_profile_enable / abg_profile_get: "mc_junction" and "mc_splice".  As `launches`, in every mode: "mc_redone"
+ * the paths merged again on the host, "mc_bytes" the bytes the splice pass wrote. */
+int abg_mc_profile(abg_mc* s, int on);
+int abg_mc_profile_get(abg_mc* s, const char* name, double* total_ms, uint64_t* launches);
+
 #ifdef __cplusplus
 }
 #endif
