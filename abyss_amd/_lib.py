@@ -74,6 +74,8 @@ def symbols():
         "abg_sg_profile_get",
         "abg_mc_create", "abg_mc_destroy", "abg_mc_last_error", "abg_mc_set_contigs", "abg_mc_merge", "abg_mc_tune", "abg_mc_profile",
         "abg_mc_profile_get",
+        "abg_pb_create", "abg_pb_destroy", "abg_pb_last_error", "abg_pb_tune", "abg_pb_align", "abg_pb_align_chain", "abg_pb_profile_get",
+        "abg_pb_profile_reset",
     ]
 
 
@@ -218,5 +220,15 @@ def load(path: str | None = None):
     lib.abg_mc_tune.argtypes = [vp, C.c_uint64, C.c_uint64]
     lib.abg_mc_profile.argtypes = [vp, C.c_int]
     lib.abg_mc_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
+    lib.abg_pb_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.abg_pb_destroy.argtypes = [vp]
+    lib.abg_pb_destroy.restype = None
+    lib.abg_pb_last_error.argtypes = [vp]
+    lib.abg_pb_last_error.restype = C.c_char_p
+    lib.abg_pb_tune.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    lib.abg_pb_align.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.POINTER(vp)]
+    lib.abg_pb_align_chain.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
+    lib.abg_pb_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
+    lib.abg_pb_profile_reset.argtypes = [vp]
     _lib = lib
     return lib

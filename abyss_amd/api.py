@@ -977,3 +977,85 @@ class PathMerge:
         ms, n = C.c_double(), C.c_uint64()
         self._lib.abg_mc_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
         return ms.value, n.value
+
+
+class BubbleAlign:
+    """PopBubbles' global alignment on one GPU (Align/alignGlobal.cc; include/abyss_amd.h abg_pb_*): for pairs of branches the number
+    of matches, the length of the consensus and the consensus; for groups of three branches and more, alignMulti's chain."""
+
+    def __init__(self, device: int = 0):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        rc = self._lib.abg_pb_create(device, C.byref(self._h))
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_pb_last_error(None)
+            self._h = None
+            raise AbyssAmdError("abg_pb_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.abg_pb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_pb_last_error(self._h)
+            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+
+    @staticmethod
+    def _flat(seqs):
+        off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        if len(seqs):
+            np.cumsum([len(s) for s in seqs], out=off[1:])
+        data = np.frombuffer(b"".join(seqs), dtype=np.uint8) if int(off[-1]) else np.zeros(1, dtype=np.uint8)
+        return data, off
+
+    def align(self, pairs, consensus: bool = False):
+        """pairs: [(a, b), ...] as bytes.  Returns (matches, size, redone) or, with consensus, (matches, size, redone, consensuses):
+        alignGlobal's matches and consensus length of every pair, whether the host aligned it because its flags fit no arena, and
+        the consensus strings as bytes."""
+        n = len(pairs)
+        a, aoff = self._flat([p[0] for p in pairs])
+        b, boff = self._flat([p[1] for p in pairs])
+        matches, size, redone = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8)
+        coff, cons = np.zeros(n + 1, dtype=np.uint64), C.c_void_p()
+        self._check(self._lib.abg_pb_align(self._h, n, a.ctypes.data, aoff.ctypes.data, b.ctypes.data, boff.ctypes.data, 1 if consensus else 0,
+                                           matches.ctypes.data, size.ctypes.data, redone.ctypes.data, coff.ctypes.data, C.byref(cons)), "abg_pb_align")
+        if not consensus:
+            return matches, size, redone.astype(bool)
+        flat = C.string_at(cons, int(coff[n])) if int(coff[n]) else b""
+        return matches, size, redone.astype(bool), [flat[int(coff[i]):int(coff[i + 1])] for i in range(n)]
+
+    def align_chain(self, groups):
+        """groups: [[branch, branch, ...], ...] as bytes, two branches or more each.  Returns (matches, size, redone, consensuses) as
+        the reference's align(seqs) gives them: the consensus so far against the next branch, round by round; matches is 0 for
+        three branches and more (alignMulti's min from 0)."""
+        n = len(groups)
+        first = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            np.cumsum([len(g) for g in groups], out=first[1:])
+        data, off = self._flat([s for g in groups for s in g])
+        matches, size, redone = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8)
+        coff, cons = np.zeros(n + 1, dtype=np.uint64), C.c_void_p()
+        self._check(self._lib.abg_pb_align_chain(self._h, n, first.ctypes.data, data.ctypes.data, off.ctypes.data, matches.ctypes.data, size.ctypes.data,
+                                                 redone.ctypes.data, coff.ctypes.data, C.byref(cons)), "abg_pb_align_chain")
+        flat = C.string_at(cons, int(coff[n])) if int(coff[n]) else b""
+        return matches, size, redone.astype(bool), [flat[int(coff[i]):int(coff[i + 1])] for i in range(n)]
+
+    def tune(self, arena_bytes: int = 0, small_limit: int = 0, batch: int = 0) -> None:
+        """bytes of flags a launch may hold, the longest side a single lane takes (at most 32), pairs a launch; 0 keeps a value"""
+        self._check(self._lib.abg_pb_tune(self._h, arena_bytes, small_limit, batch), "abg_pb_tune")
+
+    def profile_get(self, name: str) -> Tuple[float, int]:
+        ms, n = C.c_double(), C.c_uint64()
+        self._lib.abg_pb_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
+        return ms.value, n.value
+
+    def profile_reset(self) -> None:
+        self._lib.abg_pb_profile_reset(self._h)

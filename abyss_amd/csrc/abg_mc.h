@@ -137,7 +137,7 @@ inline bool mc_layout(const MCStore& st, uint32_t k, const int32_t* nodes, const
 namespace mc_detail {
 
 // isMatch, smith_waterman.cpp:65-80, with ambiguityOr / ambiguityIsSubset on characters of either case (Sequence.h:94-115)
-inline char ambiguity(char a, char b, bool isor)
+ABG_HD char ambiguity(char a, char b, bool isor) // (host and device: abg_pb.h scores with it too)
 {
 	const unsigned ma = mc_mask(mc_upper((uint8_t)a)), mb = mc_mask(mc_upper((uint8_t)b));
 	const char c = (char)mc_unmask(isor ? (ma | mb) : (ma & mb));

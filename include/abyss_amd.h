@@ -621,6 +621,41 @@ int abg_mc_tune(abg_mc* s, uint64_t tile, uint64_t batch);
 int abg_mc_profile(abg_mc* s, int on);
 int abg_mc_profile_get(abg_mc* s, const char* name, double* total_ms, uint64_t* launches);
 
+/* ---- PopBubbles: global alignment of bubble branches (Align/alignGlobal.cc, Align/alignGlobal.h:47-69) ------------------------------
+ * alignGlobal's arithmetic for many pairs at once: match 5, mismatch -4, gap open -12, gap extend -4, a match where the characters
+ * are equal or ambiguityOr of them is one of the two, the traceback in the reference's priority.  A pair gives the number of
+ * matches, the length of the consensus and, where asked, the consensus (the character or the joined code on a diagonal step, the
+ * lowercase base on a gap step).  Instead of the three score matrices a cell leaves one byte of flags in an arena of
+ * ABG_PB_ARENA_BYTES (read from the environment by abg_pb_create; default 4 GiB, allocated only as far as a launch needs); the
+ * traceback walks them on the device.  A launch takes pairs in order until their flags fill the arena or `batch` pairs are in.  A
+ * pair whose longer side is at most `small_limit` (default 16, at most 32) has a lane to itself, any other pair a wavefront.  A pair
+ * whose flags alone exceed the arena is aligned on the host by the same text and reported as redone.  Every byte must be a
+ * nucleotide or IUPAC code of either case (ABG_EINVAL otherwise; the reference asserts).
+ * An abg_pb owns a HIP stream and its buffers; one abg_pb is not thread-safe. */
+typedef struct abg_pb abg_pb;
+int abg_pb_create(int device, abg_pb** out);
+void abg_pb_destroy(abg_pb* s);
+const char* abg_pb_last_error(const abg_pb* s); /* s may be NULL: the last failed abg_pb_create */
+/* 0 keeps a value.  Changes no result. */
+int abg_pb_tune(abg_pb* s, uint64_t arena_bytes, uint64_t small_limit, uint64_t batch);
+/* Pair i is a[a_offsets[i] .. a_offsets[i + 1]] against b[b_offsets[i] .. b_offsets[i + 1]]; both offset arrays have n + 1 entries
+ * and start at 0.  matches[i], size[i] and redone[i] (1 where the host aligned it) are written for every pair.  With
+ * want_consensus the consensus of pair i is (*cons)[cons_offsets[i] .. cons_offsets[i + 1]]; without, cons_offsets is all 0.
+ * cons_offsets has n + 1 entries; *cons belongs to the abg_pb and holds until its next call. */
+int abg_pb_align(abg_pb* s, uint64_t n, const uint8_t* a, const uint64_t* a_offsets, const uint8_t* b, const uint64_t* b_offsets, int want_consensus,
+    uint32_t* matches, uint32_t* size, uint8_t* redone, uint64_t* cons_offsets, const uint8_t** cons);
+/* alignMulti for groups of branches: group g is branches group_first[g] .. group_first[g + 1] (two or more), branch j is
+ * bytes[offsets[j] .. offsets[j + 1]].  Round r aligns, for every group with at least r + 2 branches, the consensus of round r - 1
+ * (the first branch in round 0) against branch r + 1: one batch a round, the consensuses staying on the device between rounds.
+ * size[g] and the consensus are the last round's.  matches[g] is the reference's: the pair's for two branches, and min(0, ...) = 0
+ * for three or more.  redone[g] is 1 where any round of the group ran on the host. */
+int abg_pb_align_chain(abg_pb* s, uint64_t ngroups, const uint64_t* group_first, const uint8_t* bytes, const uint64_t* offsets, uint32_t* matches, uint32_t* size,
+    uint8_t* redone, uint64_t* cons_offsets, const uint8_t** cons);
+/* Kernel timing, always on: "pb_lane" and "pb_wave" (events around the launches).  As `launches`: "pb_redone" the pairs aligned on
+ * the host, "pb_cells" the cells the kernels filled, "pb_launches" the batches.  abg_pb_profile_reset zeroes all of them. */
+int abg_pb_profile_get(abg_pb* s, const char* name, double* total_ms, uint64_t* launches);
+int abg_pb_profile_reset(abg_pb* s);
+
 #ifdef __cplusplus
 }
 #endif
