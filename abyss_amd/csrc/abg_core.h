@@ -1356,6 +1356,23 @@ ABG_HD uint32_t wave_rank(bool want, uint32_t& count)
 ABG_HD uint32_t wave_rank(bool want, uint32_t& count) { count = want ? 1u : 0u; return 0; }
 #endif
 
+// Bit (i & 63) of words[i >> 6] = v.  A wavefront's lanes hold 64 consecutive i starting at a multiple of 64 (lane = i & 63; lanes
+// past the end may be inactive, the first never is when any is active): one ballot, one store.  A serial caller comes with
+// i = 0, 1, 2, ... in ascending order and sets bit after bit.  Must be reached by all active lanes together.
+#if defined(__HIP_DEVICE_COMPILE__)
+ABG_HD void wave_put_bit(uint64_t* words, uint32_t i, bool v)
+{
+	const uint64_t m = __ballot(v ? 1 : 0);
+	if (!(i & 63u)) words[i >> 6] = m;
+}
+#else
+ABG_HD void wave_put_bit(uint64_t* words, uint32_t i, bool v)
+{
+	if (!(i & 63u)) words[i >> 6] = 0;
+	words[i >> 6] |= (uint64_t)(v ? 1u : 0u) << (i & 63u);
+}
+#endif
+
 // Atomics issued by a cooperative caller (a whole wavefront in lock step, see
 // abg_core.h): lane 0 performs the operation, every lane receives its result.
 #if defined(__HIP_DEVICE_COMPILE__)

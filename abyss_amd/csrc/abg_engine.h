@@ -95,6 +95,8 @@ struct Config {
 	bool par_commit = true;           // parallel fixed-point commit (4 bytes of time stamp per filter bit) ...
 	bool overlap_bins = true;              // PASS 1: the next batch is hashed and binned on the side stream while this one is applied
 	bool overlap_purity = true;            // ... and its tiles judged there too (tile_purity reads nothing but the bins)
+	bool apply_mask = true;                // PASS 1, plain tile path: tile_apply gathers no target for a pair that cannot belong to a leader (TileEnv::amask)
+	bool lead_implicit = true;             // PASS 1, plain tile path: a k-mer met once in its batch stores no `lead` (TileEnv::lead_implicit, lead_of)
 	uint32_t dist_hash_all_ranks = 2;      // partitioned tiles: up to this many ranks, every rank hashes every op itself
 	uint32_t dist_route_min_ranks = 4;     // ... from this many ranks on, the (op, counter) pairs are routed to their owners (Engine::insert_tiles_routed); 0: never
 	uint64_t keep_insert_scratch_bytes = 16ull << 30; // PASS 1's scratch is given back before PASS 2 when larger than this
@@ -639,6 +641,9 @@ struct TileEnv {
 	uint32_t lead_js = 2;             // tile_purity: pairs of the first lead_js hash functions write `lead` (a partitioned run: all -- every rank must know)
 	uint32_t count_max = 0x7FFFFFFFu; // a counter with this many pairs or more is treated like a shared one (a partitioned run: 254 -- the ranks pass a leader's op count in a byte)
 	const uint8_t* cval = nullptr;    // partitioned run: [T x nh] 255 - (counter j of op t), combined from the ranks that own them (FDistPack2); NULL: op_verdict reads e.cnt
+	uint32_t lead_implicit = 0;       // 1: a pair that is alone on a pure counter stores no `lead` -- lead[t] == 0 then reads as "1 op, its own leader" unless the first lead_js counters are all shared (lead_of); 0 in a partitioned run, where a rank judges its own tiles only and a missing store says nothing
+	uint64_t* amask = nullptr;        // [bins][(cap + 63) / 64] bit i of a bin's words: pair i of the bin may belong to a leader -- it sits on a shared counter or is the earliest pair of a pure one; tile_purity writes it, tile_apply gathers no target for a pair whose bit is clear (any other pair of a pure counter: its op is not the earliest of its k-mer, so its target is 0).  NULL: every pair's target is gathered (partitioned runs, the sorted judge)
+	uint64_t* lead_stat = nullptr;    // [2] `lead` stores made / left out, counted where one thread runs the functors (the host-check build); NULL wherever a wavefront does
 	// the settling of k-mers that DO write shared counters (op_verdict, FCoSettle); all null / 0 when that is off
 	uint32_t* bad = nullptr;          // [(bad_mask + 1) / 32] bit "some k-mer on this counter goes through the rounds", by hashed counter position
 	uint32_t bad_mask = 0;
@@ -981,23 +986,33 @@ ABG_HDN void tile_purity(const TileEnv& e, uint64_t tile, void* fast, Sync& sy)
 		if (r.hlo != f.hlo || r.hhi != f.hhi || ((r.tj ^ f.tj) != 0 && tp_t(r) == tp_t(f))) atomic_or_u32(&info[s], 0x80000000u);
 	});
 	sy.barrier();
-	pairs([&](const TilePair& r, uint32_t, uint32_t s, uint32_t) {
+	uint64_t* amask = e.amask ? e.amask + tile * ((e.cap + 63u) >> 6) : nullptr;
+	pairs([&](const TilePair& r, uint32_t i, uint32_t s, uint32_t) {
 		const uint32_t inf = info[s], t = tp_t(r);
+		bool may_lead = true; // (what tile_apply gathers a target for: see TileEnv::amask)
 		// (a partitioned run treats a counter with 254 pairs or more like a shared one: it passes the leaders' op counts
 		// between the ranks in a byte.  Elsewhere n ops of a k-mer are n ops however many: min(m + n, 255))
 		if ((inf >> 31) || (inf & 0x7FFFFFFFu) >= e.count_max) {
 			// shared: bit j of the op's flag byte (several tiles may flag one op at once: a word-wide OR)
 			const uint32_t bit = e.p.nh <= 8 ? (1u << tp_j(r)) : 0xFFu;
 			atomic_or_u32((uint32_t*)e.opflag + (t >> 2), bit << (8 * (t & 3u)));
-			return;
+		} else {
+			// only this k-mer's ops touch the counter, one pair each: every op of the k-mer learns how many they
+			// are; the earliest leads them.  An op's pure counters all say the same, and every one of these stores is a
+			// 32-byte write transaction to a random place: the first two hash functions speak for all (an op whose first
+			// two counters are BOTH shared learns nothing and goes to the rounds -- op_verdict reads n == 0 as that)
+			// (... and a pair alone on its counter says what the reader assumes of an op nobody wrote to: lead_of)
+			const bool first_op = (uint32_t)(first[s] >> TILE_IDX_BITS) == t;
+			may_lead = first_op;
+			if (tp_j(r) < e.lead_js) {
+				if (e.lead_implicit && inf == 1u) { if (e.lead_stat) e.lead_stat[1]++; }
+				else {
+					if (e.lead_stat) e.lead_stat[0]++;
+					e.lead[t] = (inf & 0x7FFFFFFFu) | (first_op ? LEAD_BIT : 0u);
+				}
+			}
 		}
-		// only this k-mer's ops touch the counter, one pair each: every op of the k-mer learns how many they
-		// are; the earliest leads them.  An op's pure counters all say the same, and every one of these stores is a
-		// 32-byte write transaction to a random place: the first two hash functions speak for all (an op whose first
-		// two counters are BOTH shared learns nothing and goes to the rounds -- op_verdict reads n == 0 as that)
-		if (tp_j(r) >= e.lead_js) return;
-		const bool first_op = (uint32_t)(first[s] >> TILE_IDX_BITS) == t;
-		e.lead[t] = (inf & 0x7FFFFFFFu) | (first_op ? LEAD_BIT : 0u);
+		if (amask) wave_put_bit(amask, i, may_lead);
 	});
 }
 // What becomes of an op once every tile has judged its pairs.  n = the ops of its k-mer K in the batch.
@@ -1046,11 +1061,31 @@ ABG_HD bool any_bad(const TileEnv& e, uint64_t h, unsigned js)
 //    sends every candidate to the rounds when the last pass still found something.
 // (tests/hostcheck; the rule and its closure were first checked against the sequential filter in a simulation of 59
 // batches at configs[1]'s and configs[2]'s occupancy, and with counters driven into saturation: notes/README.md.)
+// What `lead` says of op t, whose flag byte is fl.  Under lead_implicit a pair that is alone on a pure counter stored nothing
+// (tile_purity, FSegJudge), and lead[t] == 0 -- what the memset left -- is read as follows: if one of the op's first lead_js
+// counters is not flagged, the op is the only one of its k-mer in the batch and leads itself (1 | LEAD_BIT); if all of them
+// are flagged, nothing is known (0: today's n == 0, the op goes to the rounds).  Why that is exactly what the stores said:
+//  * a pure counter holds exactly one pair per op of its k-mer (tile_purity), so a count of 1 on a pure counter j < lead_js
+//    means n = 1, and that op is the earliest of its k-mer's ops;
+//  * lead[t] == 0 and not every one of the first lead_js counters flagged: one of them is pure, and it stored nothing, so
+//    its count was 1 -- a count of 2 or more stores a value, and a stored value is never 0;
+//  * an op of a k-mer with n >= 2 never gets the default: its counter 0 pure stores n; counter 0 shared and counter 1 pure
+//    stores n; both shared and every bit of the mask is set.  So no op that is not its k-mer's leader is taken for one;
+//  * a bin that overflowed sets flags[0], and op_verdict returns before it looks at any of this (the sorted judge clears
+//    both arrays and applies the same rule).
+// With more than 8 hash functions a flagged op has fl == 0xFF and takes the rounds before L is looked at.
+ABG_HD uint32_t lead_of(const TileEnv& e, uint64_t t, uint32_t fl)
+{
+	const uint32_t L = e.lead[t];
+	if (L || !e.lead_implicit) return L;
+	const uint32_t mask = (1u << (e.lead_js < e.p.nh ? e.lead_js : e.p.nh)) - 1u;
+	return (fl & mask) != mask ? (1u | LEAD_BIT) : 0u;
+}
 ABG_HD void op_verdict(const TileEnv& e, uint64_t t, uint8_t& tgt, uint8_t& pend, uint32_t& centry)
 {
 	tgt = 0; pend = PEND_ROUNDS; centry = 0;
 	if (e.flags[0]) return;
-	const uint32_t fl = e.opflag[t], L = e.lead[t], n = L & ~LEAD_BIT;
+	const uint32_t fl = e.opflag[t], L = lead_of(e, t, fl), n = L & ~LEAD_BIT;
 	if (fl && (!n || e.p.nh > 8 || !e.benign)) { if (e.bad && e.p.nh <= 8) mark_bad(e, e.h0[t], fl); return; }
 	if (!fl && !(L & LEAD_BIT)) { pend = PEND_NO; return; } // (its k-mer's leader does the raising)
 	const uint64_t h = e.h0[t];
@@ -1234,8 +1269,12 @@ ABG_HDN void tile_apply(const TileEnv& e, uint64_t tile, uint8_t* lds, Sync& sy)
 	uint32_t kept = 0;
 	const bool keep = e.bad && nt >= 1024;
 	// body(pair): its target, when there is one, against the counter
-	auto raise = [&](const TilePair& r, bool first) -> bool {
-		const uint8_t tg = e.tgt[tp_t(r)];
+	// (may_lead: the pair's bit of TileEnv::amask.  A pair that cannot belong to a leader has target 0 without looking: the gather
+	// goes to tgt[0] instead -- a line every lane shares -- and its value is dropped.  The ADDRESS is selected, not the load put
+	// under a condition: a load in a conditional arm is waited for on the spot)
+	auto raise = [&](const TilePair& r, bool may_lead, bool first) -> bool {
+		const uint8_t g = e.tgt[may_lead ? tp_t(r) : 0u];
+		const uint8_t tg = may_lead ? g : (uint8_t)0;
 		if (!tg) return false;
 		// (a pure counter has one writer -- its k-mer's leader, possibly through two hash functions
 		// with the same value -- so plain byte stores do)
@@ -1247,7 +1286,11 @@ ABG_HDN void tile_apply(const TileEnv& e, uint64_t tile, uint8_t* lds, Sync& sy)
 #pragma unroll
 	for (uint32_t q = 0; q < TILE_SPLIT; q++) {
 		const TilePair* bin = e.bins + (tile * TILE_SPLIT + q) * e.cap;
-		for (uint32_t i = tid; i < nb[q]; i += nt) any |= raise(bin[i], true);
+		if (e.amask) {
+			const uint64_t* am = e.amask + (tile * TILE_SPLIT + q) * ((e.cap + 63u) >> 6);
+			for (uint32_t i = tid; i < nb[q]; i += nt) { const TilePair r = bin[i]; const uint64_t w = am[i >> 6]; any |= raise(r, ((w >> (i & 63u)) & 1u) != 0, true); }
+		} else
+		for (uint32_t i = tid; i < nb[q]; i += nt) any |= raise(bin[i], true, true);
 	}
 	if (e.bad) {
 		// a shared counter may have several writers now (op_verdict: k-mers settled together), and it ends at the largest
@@ -1261,7 +1304,7 @@ ABG_HDN void tile_apply(const TileEnv& e, uint64_t tile, uint8_t* lds, Sync& sy)
 			} else {
 				for (uint32_t q = 0; q < TILE_SPLIT; q++) {
 					const TilePair* bin = e.bins + (tile * TILE_SPLIT + q) * e.cap;
-					for (uint32_t i = tid; i < nb[q]; i += nt) again |= raise(bin[i], false);
+					for (uint32_t i = tid; i < nb[q]; i += nt) again |= raise(bin[i], true, false); // (the serial caller's passes: every target)
 				}
 			}
 		}
@@ -1328,6 +1371,8 @@ struct FSegJudge { // ... and what it then does for the pair's op
 			return;
 		}
 		if (j >= s.e.lead_js) return;
+		if (s.e.lead_implicit && cnt == 1u) { if (s.e.lead_stat) s.e.lead_stat[1]++; return; } // (tile_purity's rule: both judges leave the same `lead`)
+		if (s.e.lead_stat) s.e.lead_stat[0]++;
 		s.e.lead[t] = cnt | ((s.val[f] >> 4) == t ? LEAD_BIT : 0u);
 	}
 };
@@ -3262,6 +3307,9 @@ class Engine {
 	}
 	~Engine()
 	{
+		// (the host-check build's count of `lead` stores, for tools/count_lead_stores.py: notes/README.md)
+		if (BE::ITEM_GROUP_LOG2 == 0 && getenv("ABG_LEAD_COUNT"))
+			fprintf(stderr, "lead_stores made=%llu skipped=%llu\n", (unsigned long long)stats_.lead_stores[0], (unsigned long long)stats_.lead_stores[1]);
 		free_counters(); be_.free(vis_); if (both_) be_.free(both_); be_.free(cstate_); be_.free(scal_);
 		free_archive();
 		if (casc_.bits) be_.free(casc_.bits);
@@ -3599,7 +3647,7 @@ class Engine {
 			be_.wait_side_scope();
 			// (what was staged is now current; the other set takes the next batch)
 			std::swap(h0_, h0_alt_); std::swap(bins_, bins_alt_); std::swap(tcur_, tcur_alt_); stage_flag_ ^= 1u;
-			if (lead_alt_) { std::swap(lead_, lead_alt_); std::swap(opflag_, opflag_alt_); }
+			if (lead_alt_) { std::swap(lead_, lead_alt_); std::swap(opflag_, opflag_alt_); std::swap(amask_, amask_alt_); }
 			const bool staged = staged_ok_;
 			purity_done_ = staged && staged_purity_;
 			const uint32_t cur_flag = stage_flag_ ^ 1u; // the flag word the batch just staged wrote
@@ -3625,6 +3673,7 @@ class Engine {
 		const bool part = dist();
 		TileEnv te{ p_, cnt_, part ? own_lo_ : 0, part ? own_lo_ + own_span_ : m_, h0_alt_, bins_alt_, tile_cap_, tcur_alt_, lead_alt_ ? lead_alt_ : lead_,
 			opflag_alt_ ? opflag_alt_ : opflag_, tgt_, pendf_, flag, cfg_.benign_sharers ? 1u : 0u, part ? 16u : 2u, part ? 254u : 0x7FFFFFFFu };
+		if (!part) { te.lead_implicit = cfg_.lead_implicit ? 1u : 0u; te.lead_stat = lead_stat(); te.amask = amask_alt_; }
 		const uint64_t R = part ? (uint64_t)comm_.world : 1, me = part ? (uint64_t)comm_.rank : 0;
 		if (part && R > cfg_.dist_hash_all_ranks) {
 			// partitioned run: this rank's slice of the hashes on the side stream, the all-gather on the main
@@ -3669,6 +3718,8 @@ class Engine {
 		staged_ok_ = true;
 	}
 	bool staged_ok_ = false; uint32_t stage_flag_ = 0;
+	// where the judges count their `lead` stores: only a backend that runs the functors on one thread (ITEM_GROUP_LOG2 == 0) can
+	uint64_t* lead_stat() { return BE::ITEM_GROUP_LOG2 == 0 ? stats_.lead_stores : nullptr; }
 	bool purity_done_ = false; // the batch about to be inserted had its tiles judged while it was staged
 	std::function<void()> stage_next_; // stages the next batch; insert_range calls it once its tile kernels are queued
 
@@ -3873,6 +3924,7 @@ class Engine {
 	struct Stats { uint64_t rounds = 0, walked = 0, rewalked = 0, candidates = 0, breaks = 0, insert_rounds = 0, commit_rounds = 0, generated = 0;
 	               uint64_t bulk_calls = 0, bulk_steps = 0, lin_steps = 0, guide_slots = 0, chain_steps = 0, batch_cuts = 0, overflows = 0, memo_hits = 0, memo_adds = 0;
 	               uint64_t tiled_ops = 0, tiled_pending = 0, tile_overflows = 0, cls_covered_reads = 0, archive_bases = 0, cls_decided_reads = 0;
+	               uint64_t lead_stores[2] = { 0, 0 }; // PASS 1, host-check build only: `lead` stores the judges made / left out (TileEnv::lead_stat)
 	               uint64_t commit_rounds_incremental = 0, commit_dirty_records = 0, commit_first_chunk_decided = 0; };
 	Stats stats()
 	{
@@ -4024,6 +4076,7 @@ class Engine {
 	uint64_t* pgrp_ = nullptr; // the rounds' ops per group of PEND_GROUP ops, then their running sum (FPendCount)
 	uint8_t* wmask_ = nullptr; uint32_t* bad_ = nullptr; uint32_t* cochg_ = nullptr; // what settles k-mers writing shared counters (op_verdict)
 	uint32_t* lead_alt_ = nullptr; uint8_t* opflag_alt_ = nullptr; // ... and, when its tiles are judged there as well, of what tile_purity leaves per op
+	uint64_t* amask_ = nullptr; uint64_t* amask_alt_ = nullptr;     // ... and per pair (TileEnv::amask: a bit per pair of every bin; the second set goes with lead_alt_)
 	bool staged_purity_ = false;
 	// PASS 2 resources
 	Guide guide_{ nullptr, 0, nullptr, 0, nullptr }; uint64_t* guide_tab_ = nullptr; uint32_t guide_log2_ = 0;
@@ -4169,11 +4222,13 @@ class Engine {
 					if (cfg_.overlap_purity && !routed()) {
 						lead_alt_ = (uint32_t*)be_.alloc(nb * 4);
 						opflag_alt_ = (uint8_t*)be_.alloc(nb + 8);
+						if (cfg_.apply_mask && !dist()) amask_alt_ = (uint64_t*)be_.alloc(ntiles_ * ((tile_cap_ + 63u) >> 6) * 8);
 					}
 				}
 			}
 			lead_ = (uint32_t*)be_.alloc(nb * 4);
 			opflag_ = (uint8_t*)be_.alloc(nb + 8); // (flagged with word-wide ORs)
+			if (cfg_.apply_mask && !dist()) amask_ = (uint64_t*)be_.alloc(ntiles_ * ((tile_cap_ + 63u) >> 6) * 8);
 			tgt_ = (uint8_t*)be_.alloc(nb);
 			pendf_ = (uint8_t*)be_.alloc(nb + 8); // (read a word at a time: FPendWrite)
 			pgrp_ = (uint64_t*)be_.alloc((nb / PEND_GROUP + 2) * 8);
@@ -4230,7 +4285,8 @@ class Engine {
 		if (dist()) dres_ = (uint8_t*)be_.alloc(std::max<uint64_t>(nb, (uint64_t)cfg_.drain_threshold * 32));
 		dlost_ = (uint8_t*)be_.alloc(nb);
 		insert_scratch_bytes_ = nb * (8 + 4 + 4 + 1) + (16ull << claim_log2_);
-		if (tiled_) insert_scratch_bytes_ += ((uint64_t)ncoarse_ * coarse_cap_ + ntiles_ * tile_cap_ * (bins_alt_ ? 2 : 1)) * sizeof(TilePair) + nb * (bins_alt_ ? 15 : 7);
+		if (tiled_) insert_scratch_bytes_ += ((uint64_t)ncoarse_ * coarse_cap_ + ntiles_ * tile_cap_ * (bins_alt_ ? 2 : 1)) * sizeof(TilePair) + nb * (bins_alt_ ? 15 : 7)
+			+ ntiles_ * ((tile_cap_ + 63u) >> 6) * 8 * ((amask_ ? 1 : 0) + (amask_alt_ ? 1 : 0));
 	}
 	void free_insert()
 	{
@@ -4244,6 +4300,8 @@ class Engine {
 		}
 		if (bins_alt_) { be_.free(bins_alt_); be_.free(tcur_alt_); be_.free(h0_alt_); bins_alt_ = nullptr; tcur_alt_ = nullptr; h0_alt_ = nullptr; }
 		if (lead_alt_) { be_.free(lead_alt_); be_.free(opflag_alt_); lead_alt_ = nullptr; opflag_alt_ = nullptr; }
+		if (amask_) { be_.free(amask_); amask_ = nullptr; }
+		if (amask_alt_) { be_.free(amask_alt_); amask_alt_ = nullptr; }
 		if (dres_) { be_.free(dres_); dres_ = nullptr; }
 		be_.free(dlost_);
 		be_.free(h0_);
@@ -4294,6 +4352,7 @@ class Engine {
 			// tile; what is left goes through the reservation rounds below
 			if (!staged) flag_word = 1;
 			TileEnv te{ p_, cnt_, 0, m_, h0_, bins_, tile_cap_, tcur_, lead_, opflag_, tgt_, pendf_, pend_n_ + flag_word, cfg_.benign_sharers ? 1u : 0u };
+			te.lead_implicit = cfg_.lead_implicit ? 1u : 0u; te.lead_stat = lead_stat(); te.amask = amask_;
 			const bool judged = staged && purity_done_;
 			if (!judged) {
 				be_.memset(lead_, 0, T * 4);

@@ -111,6 +111,8 @@ class Session {
 		if (const char* e = getenv("ABG_COSETTLE_LOG2")) cfg.cosettle_log2 = (uint32_t)std::min(25, std::max(5, atoi(e))); // (tests: a table in which nearly every counter looks marked)
 		if (const char* e = getenv("ABG_LINK_DUPS")) cfg.link_duplicates = atoi(e) != 0; // the commit decides a contig's copies by their original (0: every record bit by bit)
 		if (const char* e = getenv("ABG_OVERLAP_PURITY")) cfg.overlap_purity = atoi(e) != 0; // PASS 1: the next batch's tiles judged on the side stream too
+		if (const char* e = getenv("ABG_LEAD_IMPLICIT")) cfg.lead_implicit = atoi(e) != 0; // PASS 1: a k-mer met once in its batch stores no `lead` (0: every pure pair of the first two hash functions stores)
+		if (const char* e = getenv("ABG_APPLY_MASK")) cfg.apply_mask = atoi(e) != 0; // PASS 1: tile_apply gathers no target for a pair that cannot belong to a leader (0: every pair's)
 		if (const char* e = getenv("ABG_OVERLAP_BINS")) cfg.overlap_bins = atoi(e) != 0; // the next batch hashed and binned beside this one
 		if (const char* e = getenv("ABG_PREFETCH")) cfg.prefetch_classify = atoi(e) != 0;
 		if (const char* e = getenv("ABG_ASYNC_LOAD")) cfg.async_load = atoi(e) != 0;
