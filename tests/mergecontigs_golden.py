@@ -1,7 +1,8 @@
 """Shared by the MergeContigs tests: the goldens of tests/golden/mergecontigs (made by tests/golden/make_mergecontigs.py from the
 unmodified reference), readers of their inputs, generated inputs for the GPU tests and a plain-Python restatement of the merge
 (MergePaths/MergeContigs.cpp:159-313 with Align/smith_waterman.cpp) that owes nothing to abg_mc.h: it builds the sequence as a string,
-junction by junction, as the reference does."""
+junction by junction, as the reference does.  dirty_paths() and dirty_sets() generate, over that restatement, the paths with
+content (case, N, codes, gaps, overlaps that differ, planned conflicts) that the device tests and `mc_check splice` both merge."""
 import functools
 import json
 import os
@@ -76,6 +77,7 @@ def _is_match(a, b):
     return both == a or both == b, _ambiguity(a, b, True)
 
 
+@functools.lru_cache(maxsize=None)  # (a generated path is merged again after every node it gains, and once more by the test)
 def align_overlap(a, b, verbose):
     """alignOverlap(a, b, 0, overlaps, false, verbose), smith_waterman.cpp:179-292: None, or (t_pos, h_pos, consensus, matches, print)"""
     a, b = a.decode(), b.decode()
@@ -325,3 +327,287 @@ def chains(seed, k, npaths, lengths, overlap=None, senses=None):
             at += l - ov
         paths.append((nodes, [0] + [ov] * (len(ls) - 1)))
     return contigs, paths
+
+
+# ---- generated inputs with content: case, N, codes, gaps, overlaps that differ within a path, planned conflicts
+
+def _superset(rng, c, strict=False):
+    """a code that holds every base of c, in c's case; strict: a larger one that is not N (N when there is no other)"""
+    m = MASK[c.upper()]
+    masks = [x for x in range(1, 16) if x & m == m and not (strict and x in (m, 15))] or [15]
+    out = UNMASK[rng.choice(masks)]
+    return out.lower() if c.islower() else out
+
+
+def _agree(rng, t, dirt):
+    """a head character that has a consensus with the tail character t"""
+    if t in "Nn":  # gives way to anything
+        return rng.choice("ACGT") if rng.random() >= dirt else rng.choice("NnacgtRYKMSWBDHVry")
+    if rng.random() >= dirt:
+        return t
+    return (t.lower(), rng.choice("Nn"), _superset(rng, t), _superset(rng, t, True))[rng.randrange(4)]
+
+
+def _body(rng, dirt):
+    if rng.random() >= dirt:
+        return rng.choice("ACGT")
+    return (rng.choice("Nn"), rng.choice("acgt"), rng.choice("MRWSYKVHDB"), rng.choice("mrwsykvhdb"))[rng.randrange(4)]
+
+
+def _edit(rng, t, kind):
+    """the character a planned edit puts where t is (a head character: where the tail has t)"""
+    if kind in ("N", "n"):
+        return kind
+    if kind == "lower":
+        return t.lower()
+    if kind == "code":
+        return _superset(rng, t, True)
+    m = MASK[t.upper()]
+    if kind == "solid":  # a plain base that t holds: the consensus there is no N
+        return rng.choice([b for b in "ACGT" if MASK[b] & m])
+    assert kind == "break" and m != 15, (t, kind)  # a base that t does not hold: no consensus
+    return rng.choice([b for b in "ACGT" if not MASK[b] & m])
+
+
+class Grow:
+    """One path built from left to right over the merged sequence so far, py_merge_path's.  Its contigs are appended to `contigs`."""
+
+    def __init__(self, rng, contigs, k, dirt=0.0):
+        self.rng, self.contigs, self.k, self.dirt = rng, contigs, k, dirt
+        self.nodes, self.ov, self.seq = [], [], b""
+
+    def _merged(self):
+        self.seq = py_merge_path(self.contigs, self.k, self.nodes, self.ov)[0]
+
+    def gap(self, n, ov=None):
+        """the gap of n, joined by k - 1 as MergeContigs joins it, or by `ov`"""
+        ov = self.k - 1 if ov is None else ov
+        assert self.nodes and self.nodes[-1] >= 0 and 0 < ov <= min(self.k - 1, len(self.seq)) and n > 0
+        self.nodes.append(-n)
+        self.ov.append(ov)
+        self._merged()
+
+    def contig(self, length, sense, ov=0, edits=None):
+        """a contig of `length` characters in the path's sense, the first `ov` of them a head that has a consensus with the current
+        tail (every character the same, in lower case, an N or a superset code, `dirt` of the time), the rest random; stored reverse
+        complemented where sense is true.  edits: {position in the path's sense: "lower", "N", "n", "code", "solid" or "break"}"""
+        ov = ov if self.nodes else 0
+        assert ov <= length and ov <= len(self.seq) and (ov > 0 or not self.nodes)
+        tail = self.seq[len(self.seq) - ov:].decode() if ov else ""
+        s = [_agree(self.rng, t, self.dirt) for t in tail] + [_body(self.rng, self.dirt) for _ in range(length - ov)]
+        for at, kind in sorted((edits or {}).items()):
+            s[at] = _edit(self.rng, tail[at] if at < ov else s[at], kind)
+        s = "".join(s).encode()
+        self.contigs.append(rc(s) if sense else s)
+        self.nodes.append(2 * (len(self.contigs) - 1) + bool(sense))
+        self.ov.append(ov)
+        self._merged()
+
+    def path(self):
+        return self.nodes, self.ov
+
+
+def dirty_paths(seed, k, npaths, dirt=0.15, gaps=True, breaks=None, nodes=(2, 8), overlap=(1, 90), length=None):
+    """(contigs, [(nodes, overlaps)], plan): paths of nodes[0] .. nodes[1] nodes in either sense whose junctions all have a consensus,
+    with overlaps drawn per junction, nodes that are all window, lower case, N and codes in heads and bodies, and gaps (never first,
+    last or two in a row; of 1, k - 2, k - 1, k, k + 1 and up to 2k; the head after a short gap agrees with what its window reaches
+    before the gap, since it is made from the merged tail).  length: (lo, hi) of a node's whole length, where the default is its
+    overlap and up to 120 more.  breaks: {path: (junction, position)}, junction j being that of node j with what precedes it: that
+    window gets one pair without a consensus there; such a path has no gap.  plan["flagged"]: the paths with a break."""
+    rng = random.Random(seed)
+    breaks = breaks or {}
+    contigs, paths = [], []
+    for p in range(npaths):
+        brk = breaks.get(p)
+        n = max(rng.randint(*nodes), brk[0] + 1 if brk else 0)
+        g = Grow(rng, contigs, k, dirt)
+        ahead = 0  # the overlap of the junction with the break, drawn a node early
+        while len(g.nodes) < n:
+            j = len(g.nodes)
+            if gaps and not brk and 0 < j < n - 1 and g.nodes[-1] >= 0 and len(g.seq) >= k - 1 and rng.random() < 0.25:
+                g.gap(rng.choice([1, k - 2, k - 1, k, k + 1, rng.randint(1, 2 * k)]))
+                continue
+            after_gap = j > 0 and g.nodes[-1] < 0
+            edits = {}
+            if length:
+                ln = max(rng.randint(*length), k - 1 if after_gap else 1)
+                ov = k - 1 if after_gap else min(rng.randint(*overlap), ln, len(g.seq))
+            else:
+                ov = 0 if j == 0 else k - 1 if after_gap else ahead if brk and j == brk[0] else min(rng.randint(*overlap), len(g.seq))
+                ln = ov + (0 if j and rng.random() < 0.2 else rng.randint(1, 120))
+            if brk and j == brk[0] - 1:  # the tail character of the pair: no N, and inside this node
+                ahead = rng.randint(max(brk[1] + 1, overlap[0]), max(brk[1] + 1, overlap[1]))
+                ln = max(ln, ahead)
+                edits[ln - ahead + brk[1]] = "solid"
+            if brk and j == brk[0]:
+                assert not length and ov == ahead
+                edits[brk[1]] = "break"
+            g.contig(ln, rng.random() < 0.5, ov, edits)
+        paths.append(g.path())
+    return contigs, paths, {"flagged": sorted(breaks), "breaks": dict(breaks)}
+
+
+def dump_paths(path, k, contigs, paths):
+    """what `mc_check splice` reads: "k contigs paths", a contig a line, then a path a line: its number of nodes, then node and overlap
+    of each"""
+    with open(path, "w") as f:
+        f.write("%d %d %d\n" % (k, len(contigs), len(paths)))
+        for c in contigs:
+            f.write(c.decode() + "\n")
+        for nodes, ov in paths:
+            f.write(" ".join(["%d" % len(nodes)] + ["%d %d" % (u, o) for u, o in zip(nodes, ov)]) + "\n")
+
+
+WINDOW_OVERLAPS = (63, 64, 65, 128, 129)
+
+
+def window_positions(w):
+    """the ends of a window and both sides of the second trip of a wave's lanes over it"""
+    return [q for q in sorted({0, 62, 63, 64, w - 1}) if q < w]
+
+
+def _window_set(k):
+    """paths of two nodes, ACGT but for one character: a lower-case base or an N in the tail, or a superset code in the head"""
+    rng = random.Random(2)
+    contigs, paths, marks = [], [], []
+    for kind in ("lower", "code", "N"):
+        for w in WINDOW_OVERLAPS:
+            for q in window_positions(w):
+                g = Grow(rng, contigs, k)
+                first = w + 3 + len(paths) % 40
+                g.contig(first, len(paths) & 1, 0, {first - w + q: kind} if kind != "code" else None)
+                g.contig(w + 1 + len(paths) % 23, len(paths) & 2, w, {q: kind} if kind == "code" else None)
+                marks.append((len(paths), first - w + q, kind))
+                paths.append(g.path())
+    return dict(k=k, contigs=contigs, paths=paths, marks=marks)
+
+
+CONFLICT_AT = (0, 31, 63, 64, 129)
+CONFLICTS = [(w, q, place) for place in (1, 2, 3) for w in WINDOW_OVERLAPS for q in window_positions(w)]
+CONFLICT_SETS = (len(CONFLICTS) + len(CONFLICT_AT) - 1) // len(CONFLICT_AT)
+
+
+def _conflict_set(k, which):
+    """130 paths of four nodes, ACGT only; those at CONFLICT_AT have one pair without a consensus, five of CONFLICTS in turn: the
+    overlap of the junction, the position in its window, and which of the three junctions it is"""
+    rng = random.Random(300 + which)
+    contigs, paths, breaks = [], [], {}
+    for p in range(130):
+        ovs = [WINDOW_OVERLAPS[(p + j) % 5] for j in range(3)]
+        edits = {}
+        if p in CONFLICT_AT:
+            w, q, place = CONFLICTS[(which * len(CONFLICT_AT) + CONFLICT_AT.index(p)) % len(CONFLICTS)]
+            ovs[place - 1] = w
+            edits = {place: {q: "break"}}
+            breaks[p] = (place, q)
+        g = Grow(rng, contigs, k)
+        g.contig(131 + p % 7, p & 1)
+        for j in (1, 2, 3):
+            g.contig(ovs[j - 1] + (p + j) % 9, (p >> j) & 1, min(ovs[j - 1], len(g.seq)), edits.get(j))
+        assert not edits or g.ov[breaks[p][0]] == w
+        paths.append(g.path())
+    return dict(k=k, contigs=contigs, paths=paths, flagged=sorted(breaks), breaks=breaks)
+
+
+RING_OVERLAPS = (1023, 1024, 1025)
+
+
+def _ring_sets(k):
+    """for each overlap around the ring's size a path [3000, ov, ov + 3, 2 ov + 7, 37]: the second node is all window, the last is
+    joined by 7, and lower-case marks sit at positions 0 and ov - 1 of the windows of the three large junctions (the first's in the
+    tail; the second's come down with the first's consensus; the third's in the head and in the tail).  With 20 small paths, in three
+    orders: the path the ring cannot hold in the middle, first and last."""
+    rng = random.Random(4)
+    contigs, big = [], []
+    for i, ov in enumerate(RING_OVERLAPS):
+        g = Grow(rng, contigs, k)
+        sense = lambda j: "+-+--+-+"[(i + j) % 8] == "-"
+        g.contig(3000, sense(0), 0, {3000 - ov: "lower", 2999: "lower"})
+        g.contig(ov, sense(1), ov)
+        g.contig(ov + 3, sense(2), ov, {ov + 2: "lower"})
+        g.contig(2 * ov + 7, sense(3), ov, {0: "lower"})
+        g.contig(37, sense(4), 7)
+        big.append(g.path())
+    more, small, _ = dirty_paths(5, k, 20)
+    small = [([u + 2 * len(contigs) if u >= 0 else u for u in nodes], ov) for nodes, ov in small]
+    contigs = contigs + more
+    orders = {"mid": small[:10] + [big[0], big[2], big[1]] + small[10:], "first": [big[2], big[0], big[1]] + small, "last": small + big}
+    return {"ring." + name: dict(k=k, contigs=contigs, paths=paths, host=[i for i, (_, ov) in enumerate(paths) if max(ov) > 1024])
+            for name, paths in orders.items()}
+
+
+GAP_SIZES = (1, 15, 16, 17, 23, 24, 25, 26, 40)
+
+
+def _gap_set(k):
+    """[contig, gap n, contig] for every n of GAP_SIZES, the first contig as long as puts the gap's first own byte at offsets 0, 1 and
+    15 of a 16-byte chunk of the flat output of one batch"""
+    rng = random.Random(6)
+    contigs, paths, gap_at, at = [], [], [], 0
+    for target in (0, 1, 15):
+        for n in GAP_SIZES:
+            g = Grow(rng, contigs, k, 0.15)
+            first = 30 + len(paths) % 5
+            first += (target - at - first) % 16
+            g.contig(first, len(paths) & 1)
+            g.gap(n)
+            g.contig(k - 1 + 5 + len(paths) % 19, len(paths) & 2, k - 1)
+            gap_at.append((at + first, target))
+            at += len(g.seq)
+            paths.append(g.path())
+    return dict(k=k, contigs=contigs, paths=paths, gap_at=gap_at)
+
+
+def _short_gap_set(k):
+    """[contig, gap n, contig] with the gap joined by fewer than k - 1 and the contig after it by fewer than n.  Joined by k - 1 on
+    both sides, as in every other set, a gap keeps bytes of its own in the layout only when n >= k, and those are all N: its k - 1
+    leading N lie in the window before it, and n < k of n lie in the window after it, which the consensus writes.  Only these paths
+    lay out the N run and the n run of one gap (n < k) side by side, and any n run at all."""
+    rng = random.Random(9)
+    contigs, paths = [], []
+    for n in (2, 5, 16, 17, k - 1, k, 40):
+        for before in (1, 7, k - 2):
+            for after in (1, 3):
+                if after < n:
+                    g = Grow(rng, contigs, k, 0.15)
+                    g.contig(26 + len(paths) % 16, len(paths) & 1)
+                    g.gap(n, before)
+                    g.contig(after + 4 + len(paths) % 21, len(paths) & 2, after)
+                    paths.append(g.path())
+    return dict(k=k, contigs=contigs, paths=paths)
+
+
+DIRTY_SETS = ("dirty", "dirty.breaks", "window") + tuple("conflict.%d" % which for which in range(CONFLICT_SETS)) + \
+    ("ring.mid", "ring.first", "ring.last", "gaps", "gaps.short", "seams")
+
+
+@functools.lru_cache(maxsize=None)
+def dirty_sets():
+    """the generated sets of the device tests, which tests/test_mergecontigs_host.py runs through `mc_check splice` too:
+    name -> dict(k, contigs, paths, flagged: paths with a junction that has no consensus, host: paths the ring cannot hold, ...)"""
+    k = 25
+    sets = {}
+    contigs, paths, plan = dirty_paths(1, k, 257)
+    sets["dirty"] = dict(k=k, contigs=contigs, paths=paths, flagged=plan["flagged"])
+    contigs, paths, plan = dirty_paths(7, k, 40, breaks={0: (1, 0), 5: (3, 17), 11: (2, 89), 39: (7, 40)})
+    sets["dirty.breaks"] = dict(k=k, contigs=contigs, paths=paths, flagged=plan["flagged"], breaks=plan["breaks"])
+    sets["window"] = _window_set(k)
+    for which in range(CONFLICT_SETS):
+        sets["conflict.%d" % which] = _conflict_set(k, which)
+    sets.update(_ring_sets(k))
+    sets["gaps"] = _gap_set(k)
+    sets["gaps.short"] = _short_gap_set(k)
+    contigs, paths, plan = dirty_paths(8, k, 64, dirt=0.2, gaps=False, nodes=(8, 8), overlap=(1, 3), length=(1, 5))
+    sets["seams"] = dict(k=k, contigs=contigs, paths=paths, flagged=plan["flagged"])
+    for s in sets.values():
+        s.setdefault("flagged", [])
+        s.setdefault("host", [])
+    assert tuple(sets) == DIRTY_SETS
+    return sets
+
+
+@functools.lru_cache(maxsize=None)
+def expected(name):
+    """py_merge_path of every path of a set of dirty_sets(): [(sequence, flagged, log)], computed once"""
+    s = dirty_sets()[name]
+    return tuple(py_merge_path(s["contigs"], s["k"], nodes, ov) for nodes, ov in s["paths"])
