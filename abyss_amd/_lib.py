@@ -76,6 +76,7 @@ def symbols():
         "abg_mc_profile_get",
         "abg_pb_create", "abg_pb_destroy", "abg_pb_last_error", "abg_pb_tune", "abg_pb_align", "abg_pb_align_chain", "abg_pb_profile_get",
         "abg_pb_profile_reset",
+        "abg_mp_create", "abg_mp_destroy", "abg_mp_last_error", "abg_mp_tune", "abg_mp_align", "abg_mp_profile_get", "abg_mp_profile_reset",
     ]
 
 
@@ -230,5 +231,14 @@ def load(path: str | None = None):
     lib.abg_pb_align_chain.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
     lib.abg_pb_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
     lib.abg_pb_profile_reset.argtypes = [vp]
+    lib.abg_mp_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.abg_mp_destroy.argtypes = [vp]
+    lib.abg_mp_destroy.restype = None
+    lib.abg_mp_last_error.argtypes = [vp]
+    lib.abg_mp_last_error.restype = C.c_char_p
+    lib.abg_mp_tune.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64]
+    lib.abg_mp_align.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, C.c_uint32, C.c_float, vp]
+    lib.abg_mp_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
+    lib.abg_mp_profile_reset.argtypes = [vp]
     _lib = lib
     return lib

@@ -1059,3 +1059,60 @@ class BubbleAlign:
 
     def profile_reset(self) -> None:
         self._lib.abg_pb_profile_reset(self._h)
+
+
+class PairMerge:
+    """abyss-mergepairs' overlap alignment on one GPU (Align/mergepairs.cc, Align/smith_waterman.cpp; include/abyss_amd.h abg_mp_*):
+    for every pair of reads, how many overlaps of read 1 with the reverse complement of read 2 the reference keeps, how many pass
+    each of its filters, and the one overlap to merge by when exactly one is left."""
+
+    FIELDS = ("n_aligned", "n_matches", "n_identity", "n_gapless", "t_pos", "h_pos", "length", "matches", "flags", "reserved")
+    ORDER_DEPENDENT, HOST, BREAK_TAKEN, BREAK_NOT_TAKEN = 1, 2, 4, 8
+
+    def __init__(self, device: int = 0):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        rc = self._lib.abg_mp_create(device, C.byref(self._h))
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_mp_last_error(None)
+            self._h = None
+            raise AbyssAmdError("abg_mp_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.abg_mp_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != _lib.ABG_OK:
+            msg = self._lib.abg_mp_last_error(self._h)
+            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+
+    def align(self, pairs, min_matches: int = 10, identity: float = 0.9):
+        """pairs: [(read 1, read 2), ...] as bytes, as the files hold them.  Returns an (n, 10) array of uint32, a row a pair, its
+        columns named by FIELDS."""
+        n = len(pairs)
+        a, aoff = BubbleAlign._flat([p[0] for p in pairs])
+        b, boff = BubbleAlign._flat([p[1] for p in pairs])
+        records = np.zeros((n, len(self.FIELDS)), dtype=np.uint32)
+        self._check(self._lib.abg_mp_align(self._h, n, a.ctypes.data, aoff.ctypes.data, b.ctypes.data, boff.ctypes.data, min_matches, identity,
+                                           records.ctypes.data), "abg_mp_align")
+        return records
+
+    def tune(self, max_len: int = 0, spill_bytes: int = 0, batch: int = 0) -> None:
+        """the longest read the kernel takes (at most 512), bytes of spilled rows a launch may hold, pairs a launch; 0 keeps a value"""
+        self._check(self._lib.abg_mp_tune(self._h, max_len, spill_bytes, batch), "abg_mp_tune")
+
+    def profile_get(self, name: str) -> Tuple[float, int]:
+        ms, n = C.c_double(), C.c_uint64()
+        self._lib.abg_mp_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
+        return ms.value, n.value
+
+    def profile_reset(self) -> None:
+        self._lib.abg_mp_profile_reset(self._h)

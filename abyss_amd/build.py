@@ -61,6 +61,7 @@ UNITS = {
     "abg_sg": ["abg_sg.hip", "abg_sg.h", "abg_core.h"],
     "abg_mc": ["abg_mc.hip", "abg_mc.h", "abg_ov.h", "abg_core.h"],
     "abg_pb": ["abg_pb.hip", "abg_pb.h", "abg_mc.h", "abg_ov.h", "abg_core.h"],
+    "abg_mp": ["abg_mp.hip", "abg_mp.h", "abg_mc.h", "abg_ov.h", "abg_core.h"],
 }
 # flags a unit adds to the common command line (abg_de: its sums must match a serial evaluation bit for bit, so no product may be
 # fused into an add, on the device or in the host tail)
@@ -112,7 +113,7 @@ def build_cli(force: bool = False) -> str:
               "-L" + os.path.dirname(LIB), "-labyss_amd", "-Wl,-rpath,$ORIGIN/../lib", "-lpthread"])
         for name, main in (("abyss-map", "map_main.cc"), ("abyss-index", "index_main.cc"), ("DistanceEst", "distanceest_main.cc"),
                            ("Overlap", "overlap_main.cc"), ("SimpleGraph", "simplegraph_main.cc"), ("MergeContigs", "mergecontigs_main.cc"),
-                           ("PopBubbles", "popbubbles_main.cc")):
+                           ("PopBubbles", "popbubbles_main.cc"), ("abyss-mergepairs", "mergepairs_main.cc")):
             _run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-o",
                   os.path.join(BIN_DIR, name), os.path.join(CSRC, "host", main),
                   "-L" + os.path.dirname(LIB), "-labyss_amd", "-Wl,-rpath,$ORIGIN/../lib", "-lpthread"] +
@@ -140,6 +141,7 @@ OV_CHECK = os.path.join(ROOT, "tests", "hostcheck", "ov_check")
 SG_CHECK = os.path.join(ROOT, "tests", "hostcheck", "sg_check")
 MC_CHECK = os.path.join(ROOT, "tests", "hostcheck", "mc_check")
 PB_CHECK = os.path.join(ROOT, "tests", "hostcheck", "pb_check")
+MP_CHECK = os.path.join(ROOT, "tests", "hostcheck", "mp_check")
 
 
 def build_hostcheck(force: bool = False) -> str:
@@ -193,6 +195,11 @@ def build_hostcheck(force: bool = False) -> str:
         [os.path.join(CSRC, "host", f) for f in ("popbubbles_core.h", "rresolver_core.h", "graph_writers.h", "fasta_reader.h", "si_bytes.h")]
     if force or _newer(PB_CHECK, pdeps):
         _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", PB_CHECK, psrc, "-lpthread"])
+    qsrc = os.path.join(ROOT, "tests", "hostcheck", "mp_check.cc")
+    qdeps = [qsrc] + [os.path.join(CSRC, f) for f in ("abg_mp.h", "abg_mc.h", "abg_ov.h", "abg_core.h")] + \
+        [os.path.join(CSRC, "host", f) for f in ("mergepairs_core.h", "fasta_reader.h")]
+    if force or _newer(MP_CHECK, qdeps):
+        _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", MP_CHECK, qsrc, "-lpthread"])
     return HOSTCHECK
 
 

@@ -105,7 +105,13 @@ class FastaReader {
 	// next record; false at end of file
 	bool read(std::string& id, std::string& comment, std::string& s)
 	{
-		std::string q, header, line;
+		std::string q;
+		return read(id, comment, s, q);
+	}
+	// the same with the record's quality (empty for FASTA), as FastqRecord's operator>> has it
+	bool read(std::string& id, std::string& comment, std::string& s, std::string& q)
+	{
+		std::string header, line;
 		for (;;) {
 			id.clear(); comment.clear(); q.clear(); s.clear();
 			while (peek() == '#') getline(line);
@@ -131,6 +137,7 @@ class FastaReader {
 			bool skip = false;
 			if (comment.size() > 3 && comment[1] == ':' && comment[3] == ':') { // Casava
 				if (m_opt.chastityFilter && comment[2] == 'Y') {
+					m_unchaste++;
 					if (type == '@') { getline(line); getline(line); getline(line); }
 					else { while (peek() != '>' && peek() != '#' && getline(line)) {} }
 					skip = true;
@@ -170,6 +177,11 @@ class FastaReader {
 	bool finish(std::string& s, std::string& q, unsigned qoff_default)
 	{
 		unsigned qoff = m_opt.qualityOffset > 0 ? (unsigned)m_opt.qualityOffset : qoff_default;
+		if (m_max_length > 0) { // FastaReader.cpp:362-367: from the 3' end, before the quality trimming
+			// (the reference's erase throws where the sequence or the quality is shorter than that, and the process ends there)
+			if ((size_t)m_max_length > s.size() || (size_t)m_max_length > q.size()) m_beyond = true;
+			else { s.erase((size_t)m_max_length); q.erase((size_t)m_max_length); }
+		}
 		if (m_opt.qualityThreshold > 0 && !q.empty()) {
 			// keep [first base with q >= threshold, last such base]
 			int good = (int)qoff + m_opt.qualityThreshold;
@@ -224,7 +236,7 @@ class FastaReader {
 		if (f.size() >= 11 && (f[9].size() == f[10].size() || f[10] == "*")) { // SAM
 			unsigned flags = (unsigned)strtoul(f[1].c_str(), NULL, 0);
 			if (flags & 0x100) return 0;                         // FSECONDARY
-			if (m_opt.chastityFilter && (flags & 0x200)) return 0; // FQCFAIL
+			if (m_opt.chastityFilter && (flags & 0x200)) { m_unchaste++; return 0; } // FQCFAIL
 			id = f[0];
 			char which = '0';
 			switch (flags & 0xc1) { // FPAIRED|FREAD1|FREAD2
@@ -252,7 +264,7 @@ class FastaReader {
 			bool ok;
 			bool ch = chaste(f.back(), ok);
 			if (!ok) die("chastity filter should be one of 0, 1, N or Y");
-			if (m_opt.chastityFilter && !ch) return 0;
+			if (m_opt.chastityFilter && !ch) { m_unchaste++; return 0; }
 			id = f[0];
 			for (int i = 1; i < 6; i++) if (!f[i].empty()) { id += ':'; id += f[i]; }
 			if (!f[6].empty() && f[6] != "0") { id += '#'; id += f[6]; }
@@ -302,8 +314,16 @@ class FastaReader {
   public:
 	// this reader runs on one of several parser threads (SequenceReader, read_fasta_blocks): see die()
 	void on_worker_thread() { m_worker = true; }
+	// FastaReader's third argument: sequences are cut to this length, 0 for no limit.  beyond(): a record was shorter than it.
+	void set_max_length(int n) { m_max_length = n; }
+	bool beyond() const { return m_beyond; }
+	// the records the chastity filter has dropped so far
+	unsigned unchaste() const { return m_unchaste; }
   private:
 	bool m_worker = false;
+	int m_max_length = 0;
+	bool m_beyond = false;
+	unsigned m_unchaste = 0;
 };
 
 // Compressed inputs decompressed AHEAD: every one by a decompressor child of its own (gunzip -c

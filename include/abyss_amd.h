@@ -656,6 +656,43 @@ int abg_pb_align_chain(abg_pb* s, uint64_t ngroups, const uint64_t* group_first,
 int abg_pb_profile_get(abg_pb* s, const char* name, double* total_ms, uint64_t* launches);
 int abg_pb_profile_reset(abg_pb* s);
 
+/* ---- abyss-mergepairs: overlap alignment of read pairs (Align/mergepairs.cc, Align/smith_waterman.cpp alignOverlap) --------------
+ * For every pair, read 1 against the reverse complement of read 2 with match 1, mismatch -2 and gaps of -10000, isMatch aware of
+ * case and IUPAC codes; then the reference's choice among the last row's columns, and its three filters: matches >= min_matches,
+ * !(matches / length < identity), no gap.  A pair gives one record.  The kernel keeps no matrix: what a backtrack would return is
+ * carried through the recurrence, and only the last row is looked at.  Where the reference's answer depends on the order std::sort
+ * leaves equal scores in, the kernel spills the last row into an arena of ABG_MP_SPILL_BYTES (default 64 MiB) and the host sorts
+ * it with the reference's own call; pairs that found the arena full go out again.  A pair with a read longer than ABG_MP_MAX_LEN
+ * (default and at most 512), or with a byte of 128 and above, is aligned on the host by the same text.  A call's pairs go out in
+ * batches of ABG_MP_BATCH (default 65,536) on two streams.  The three variables are read by abg_mp_create and change no result.
+ * Every byte of b must have a complement (ABG_EINVAL otherwise; the reference aborts), a read is at most 100,000 bytes.
+ * An abg_mp owns two HIP streams and their buffers; one abg_mp is not thread-safe. */
+typedef struct abg_mp abg_mp;
+typedef struct abg_mp_record {
+	uint32_t n_aligned, n_matches, n_identity, n_gapless; /* the overlaps alignOverlap returns, and how many are left after each filter */
+	uint32_t t_pos, h_pos, length, matches;               /* the one that is left when n_gapless is 1; 0 otherwise */
+	uint32_t flags;                                       /* ABG_MP_* */
+	uint32_t reserved;
+} abg_mp_record;
+#define ABG_MP_ORDER_DEPENDENT 1u /* the answer depended on std::sort's order of equal scores: the host replayed the loop */
+#define ABG_MP_HOST 2u            /* the host aligned the pair */
+#define ABG_MP_BREAK_TAKEN 4u     /* the loop broke after its first alignment */
+#define ABG_MP_BREAK_NOT_TAKEN 8u /* the loop found an alignment and went on */
+int abg_mp_create(int device, abg_mp** out);
+void abg_mp_destroy(abg_mp* s);
+const char* abg_mp_last_error(const abg_mp* s); /* s may be NULL: the last failed abg_mp_create */
+/* 0 keeps a value.  Changes no result. */
+int abg_mp_tune(abg_mp* s, uint64_t max_len, uint64_t spill_bytes, uint64_t batch);
+/* Pair i is read 1 a[a_offsets[i] .. a_offsets[i + 1]] and read 2 b[b_offsets[i] .. b_offsets[i + 1]], both as the files hold
+ * them; both offset arrays have n + 1 entries and start at 0.  records[i] is written for every pair. */
+int abg_mp_align(abg_mp* s, uint64_t n, const uint8_t* a, const uint64_t* a_offsets, const uint8_t* b, const uint64_t* b_offsets, uint32_t min_matches, float identity,
+    abg_mp_record* records);
+/* Kernel timing, always on: "mp_wave" (events around the launches).  As `launches`: "mp_spilled" the pairs whose last row the host
+ * sorted, "mp_host" the pairs the host aligned, "mp_relaunched" the pairs sent out again for want of room in the arena, "mp_cells"
+ * the cells the kernel filled, "mp_launches" the batches.  abg_mp_profile_reset zeroes all of them. */
+int abg_mp_profile_get(abg_mp* s, const char* name, double* total_ms, uint64_t* launches);
+int abg_mp_profile_reset(abg_mp* s);
+
 #ifdef __cplusplus
 }
 #endif
