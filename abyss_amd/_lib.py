@@ -46,6 +46,11 @@ TEXT_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint64)
 
 _lib = None
 
+# the stage families of include/abyss_amd.h (abg_<prefix>_*) and whether profiling is switched (abg_XX_profile) or always on
+# (abg_XX_profile_reset)
+STAGE_PREFIXES = [("abg_overlap", True), ("abg_rr", True), ("abg_kn", True), ("abg_fm", True), ("abg_de", True), ("abg_ov", True),
+                  ("abg_sg", True), ("abg_mc", True), ("abg_pb", False), ("abg_mp", False)]
+
 
 def symbols():
     """Every entry point include/abyss_amd.h declares."""
@@ -132,19 +137,9 @@ def load(path: str | None = None):
     lib.abg_dev_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
     lib.abg_dev_free.argtypes = [vp, vp]
     lib.abg_overlap_create.argtypes = [C.c_int, C.POINTER(vp)]
-    lib.abg_overlap_destroy.argtypes = [vp]
-    lib.abg_overlap_destroy.restype = None
-    lib.abg_overlap_last_error.argtypes = [vp]
-    lib.abg_overlap_last_error.restype = C.c_char_p
     lib.abg_overlap_join.argtypes = [vp, C.c_uint32, C.c_uint64, vp, vp, C.c_int, u64p]
     lib.abg_overlap_edges.argtypes = [vp, vp, vp]
-    lib.abg_overlap_profile.argtypes = [vp, C.c_int]
-    lib.abg_overlap_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
     lib.abg_rr_create.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(vp)]
-    lib.abg_rr_destroy.argtypes = [vp]
-    lib.abg_rr_destroy.restype = None
-    lib.abg_rr_last_error.argtypes = [vp]
-    lib.abg_rr_last_error.restype = C.c_char_p
     lib.abg_rr_bytes.argtypes = [vp, u64p]
     lib.abg_rr_clear.argtypes = [vp]
     lib.abg_rr_insert_seqs.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, u64p]
@@ -152,13 +147,7 @@ def load(path: str | None = None):
     lib.abg_rr_popcount.argtypes = [vp, u64p]
     lib.abg_rr_export.argtypes = [vp, vp]
     lib.abg_rr_sync.argtypes = [vp]
-    lib.abg_rr_profile.argtypes = [vp, C.c_int]
-    lib.abg_rr_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
     lib.abg_kn_create.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(vp)]
-    lib.abg_kn_destroy.argtypes = [vp]
-    lib.abg_kn_destroy.restype = None
-    lib.abg_kn_last_error.argtypes = [vp]
-    lib.abg_kn_last_error.restype = C.c_char_p
     lib.abg_kn_import.argtypes = [vp, C.c_uint32, vp]
     lib.abg_kn_export.argtypes = [vp, C.c_uint32, vp]
     lib.abg_kn_insert_seqs.argtypes = [vp, vp, vp, C.c_uint64]
@@ -166,79 +155,47 @@ def load(path: str | None = None):
     lib.abg_kn_popcount.argtypes = [vp, vp]
     lib.abg_kn_hash_seq.argtypes = [vp, C.c_char_p, C.c_uint64, vp, vp, vp]
     lib.abg_kn_sync.argtypes = [vp]
-    lib.abg_kn_profile.argtypes = [vp, C.c_int]
-    lib.abg_kn_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
     lib.abg_fm_create.argtypes = [C.c_int, C.POINTER(vp)]
-    lib.abg_fm_destroy.argtypes = [vp]
-    lib.abg_fm_destroy.restype = None
-    lib.abg_fm_last_error.argtypes = [vp]
-    lib.abg_fm_last_error.restype = C.c_char_p
     lib.abg_fm_build.argtypes = [vp, vp, C.c_uint64]
     lib.abg_fm_size.argtypes = [vp, u64p]
     lib.abg_fm_export.argtypes = [vp, vp, vp]
     lib.abg_fm_map_seqs.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]
     lib.abg_fm_sync.argtypes = [vp]
     lib.abg_fm_tune.argtypes = [vp, C.c_uint32]
-    lib.abg_fm_profile.argtypes = [vp, C.c_int]
-    lib.abg_fm_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
     lib.abg_de_create.argtypes = [C.c_int, C.POINTER(vp)]
-    lib.abg_de_destroy.argtypes = [vp]
-    lib.abg_de_destroy.restype = None
-    lib.abg_de_last_error.argtypes = [vp]
-    lib.abg_de_last_error.restype = C.c_char_p
     lib.abg_de_set_pmf.argtypes = [vp, vp, C.c_uint64, C.c_double, C.c_double]
     lib.abg_de_scan.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]
     lib.abg_de_estimate.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp]
     lib.abg_de_tune.argtypes = [vp, C.c_uint32]
-    lib.abg_de_profile.argtypes = [vp, C.c_int]
-    lib.abg_de_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
     lib.abg_ov_create.argtypes = [C.c_int, C.POINTER(vp)]
-    lib.abg_ov_destroy.argtypes = [vp]
-    lib.abg_ov_destroy.restype = None
-    lib.abg_ov_last_error.argtypes = [vp]
-    lib.abg_ov_last_error.restype = C.c_char_p
     lib.abg_ov_set_contigs.argtypes = [vp, vp, vp, C.c_uint64]
     lib.abg_ov_find.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, vp, vp, C.POINTER(vp)]
-    lib.abg_ov_profile.argtypes = [vp, C.c_int]
-    lib.abg_ov_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
     lib.abg_sg_create.argtypes = [C.c_int, C.POINTER(vp)]
-    lib.abg_sg_destroy.argtypes = [vp]
-    lib.abg_sg_destroy.restype = None
-    lib.abg_sg_last_error.argtypes = [vp]
-    lib.abg_sg_last_error.restype = C.c_char_p
     lib.abg_sg_set_graph.argtypes = [vp, C.c_uint64, vp, vp, vp, vp]
     lib.abg_sg_search.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]
     lib.abg_sg_tune.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]
-    lib.abg_sg_profile.argtypes = [vp, C.c_int]
-    lib.abg_sg_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
     lib.abg_mc_create.argtypes = [C.c_int, C.POINTER(vp)]
-    lib.abg_mc_destroy.argtypes = [vp]
-    lib.abg_mc_destroy.restype = None
-    lib.abg_mc_last_error.argtypes = [vp]
-    lib.abg_mc_last_error.restype = C.c_char_p
     lib.abg_mc_set_contigs.argtypes = [vp, vp, vp, C.c_uint64]
     lib.abg_mc_merge.argtypes = [vp, C.c_uint32, C.c_uint64, vp, vp, vp, C.c_int, vp, vp, C.POINTER(vp), vp, vp, C.POINTER(vp)]
     lib.abg_mc_tune.argtypes = [vp, C.c_uint64, C.c_uint64]
-    lib.abg_mc_profile.argtypes = [vp, C.c_int]
-    lib.abg_mc_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
     lib.abg_pb_create.argtypes = [C.c_int, C.POINTER(vp)]
-    lib.abg_pb_destroy.argtypes = [vp]
-    lib.abg_pb_destroy.restype = None
-    lib.abg_pb_last_error.argtypes = [vp]
-    lib.abg_pb_last_error.restype = C.c_char_p
     lib.abg_pb_tune.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64]
     lib.abg_pb_align.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.POINTER(vp)]
     lib.abg_pb_align_chain.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
-    lib.abg_pb_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
-    lib.abg_pb_profile_reset.argtypes = [vp]
     lib.abg_mp_create.argtypes = [C.c_int, C.POINTER(vp)]
-    lib.abg_mp_destroy.argtypes = [vp]
-    lib.abg_mp_destroy.restype = None
-    lib.abg_mp_last_error.argtypes = [vp]
-    lib.abg_mp_last_error.restype = C.c_char_p
     lib.abg_mp_tune.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64]
     lib.abg_mp_align.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, C.c_uint32, C.c_float, vp]
-    lib.abg_mp_profile_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
-    lib.abg_mp_profile_reset.argtypes = [vp]
+    # what every stage family has: destroy, last_error and profile_get; a profiling switch, or (always timing) a reset
+    for prefix, switched in STAGE_PREFIXES:
+        fn = lambda name: getattr(lib, "%s_%s" % (prefix, name))  # noqa: E731
+        fn("destroy").argtypes = [vp]
+        fn("destroy").restype = None
+        fn("last_error").argtypes = [vp]
+        fn("last_error").restype = C.c_char_p
+        fn("profile_get").argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), u64p]
+        if switched:
+            fn("profile").argtypes = [vp, C.c_int]
+        else:
+            fn("profile_reset").argtypes = [vp]
     _lib = lib
     return lib

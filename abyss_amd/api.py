@@ -335,22 +335,30 @@ def pack_ends(seqs: Sequence[bytes], overlap: int) -> Tuple[np.ndarray, np.ndarr
     return out[0], out[1]
 
 
-class OverlapJoin:
-    """AdjList's join of contig ends overlapping by exactly k-1 bases, on one GPU
-    (buildOverlapGraph, AdjList/AdjList.cpp:233-263; include/abyss_amd.h abg_overlap_*)."""
+class _Handle:
+    """What the handle classes over one abg_XX_* family of include/abyss_amd.h share: creation and its error text, close, the check
+    of a return code and profile_get.  `_prefix` selects the family."""
+
+    _prefix = ""
 
     def __init__(self, device: int = 0):
+        self._create(device)
+
+    def _fn(self, name):
+        return getattr(self._lib, "%s_%s" % (self._prefix, name))
+
+    def _create(self, device, *create_args):
         self._lib = _lib.load()
         self._h = C.c_void_p()
-        rc = self._lib.abg_overlap_create(device, C.byref(self._h))
+        rc = self._fn("create")(device, *create_args, C.byref(self._h))
         if rc != _lib.ABG_OK:
-            msg = self._lib.abg_overlap_last_error(None)
+            msg = self._fn("last_error")(None)
             self._h = None
-            raise AbyssAmdError("abg_overlap_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
+            raise AbyssAmdError("%s_create failed (%d): %s" % (self._prefix, rc, msg.decode() if msg else ""))
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.abg_overlap_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -361,8 +369,43 @@ class OverlapJoin:
 
     def _check(self, rc, what):
         if rc != _lib.ABG_OK:
-            msg = self._lib.abg_overlap_last_error(self._h)
+            msg = self._fn("last_error")(self._h)
             raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+
+    def profile_get(self, name: str) -> Tuple[float, int]:
+        ms, n = C.c_double(), C.c_uint64()
+        self._fn("profile_get")(self._h, name.encode(), C.byref(ms), C.byref(n))
+        return ms.value, n.value
+
+
+class _SwitchedHandle(_Handle):
+    """a stage that times its launches only while profiling is switched on"""
+
+    def profile(self, on: bool = True) -> None:
+        self._fn("profile")(self._h, int(on))
+
+
+class _TimedHandle(_Handle):
+    """a stage that always times its launches and counts from zero again after a reset"""
+
+    def profile_reset(self) -> None:
+        self._fn("profile_reset")(self._h)
+
+
+def _flat(seqs):
+    """sequences as one uint8 array (one byte where there is none: its address is taken) and their n + 1 offsets"""
+    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    if len(seqs):
+        np.cumsum([len(s) for s in seqs], out=off[1:])
+    data = np.frombuffer(b"".join(seqs), dtype=np.uint8) if int(off[-1]) else np.zeros(1, dtype=np.uint8)
+    return data, off
+
+
+class OverlapJoin(_SwitchedHandle):
+    """AdjList's join of contig ends overlapping by exactly k-1 bases, on one GPU
+    (buildOverlapGraph, AdjList/AdjList.cpp:233-263; include/abyss_amd.h abg_overlap_*)."""
+
+    _prefix = "abg_overlap"
 
     def join(self, overlap: int, head: np.ndarray, tail: np.ndarray, strand_specific: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """(offsets [2n+1], targets): out-edges of vertex s (2i = i+, 2i+1 = i-) are targets[offsets[s]:offsets[s+1]]."""
@@ -376,14 +419,6 @@ class OverlapJoin:
         tgt = np.zeros(ne.value, dtype=np.uint32)
         self._check(self._lib.abg_overlap_edges(self._h, off.ctypes.data, tgt.ctypes.data if ne.value else None), "abg_overlap_edges")
         return off, tgt
-
-    def profile(self, on: bool = True) -> None:
-        self._lib.abg_overlap_profile(self._h, int(on))
-
-    def profile_get(self, name: str) -> Tuple[float, int]:
-        ms, n = C.c_double(), C.c_uint64()
-        self._lib.abg_overlap_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
-        return ms.value, n.value
 
 
 def counting_bloom_file(counters: np.ndarray, k: int, num_hashes: int) -> bytes:
@@ -443,34 +478,14 @@ def format_read_log(results: np.ndarray, read_ids: Sequence[bytes]) -> bytes:
     return b"".join(rows)
 
 
-class ReadFilter:
+class ReadFilter(_SwitchedHandle):
     """The Bloom filter of the reads' r-mers that abyss-rresolver-short keeps per r value, on one GPU
     (btllib::KmerBloomFilter as RResolver/BloomFilters.cpp:139-264 uses it; include/abyss_amd.h abg_rr_*)."""
 
+    _prefix = "abg_rr"
+
     def __init__(self, nbytes: int, r: int, hash_num: int = 7, device: int = 0):
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
-        rc = self._lib.abg_rr_create(device, nbytes, hash_num, r, C.byref(self._h))
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_rr_last_error(None)
-            self._h = None
-            raise AbyssAmdError("abg_rr_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.abg_rr_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_rr_last_error(self._h)
-            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+        self._create(device, nbytes, hash_num, r)
 
     @property
     def nbytes(self) -> int:
@@ -510,46 +525,18 @@ class ReadFilter:
         self._check(self._lib.abg_rr_export(self._h, out.ctypes.data), "abg_rr_export")
         return out
 
-    def profile(self, on: bool = True) -> None:
-        self._lib.abg_rr_profile(self._h, int(on))
 
-    def profile_get(self, name: str) -> Tuple[float, int]:
-        ms, n = C.c_double(), C.c_uint64()
-        self._lib.abg_rr_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
-        return ms.value, n.value
-
-
-class KonnectorBloom:
+class KonnectorBloom(_SwitchedHandle):
     """A Konnector Bloom filter on one GPU: `abyss-bloom build -t konnector` (Bloom/BloomFilter.h, CascadingBloomFilter.h,
     BloomFilterWindow.h; include/abyss_amd.h abg_kn_*).  `bits` is the index space (hash % bits); the filter holds `levels`
     levels of its window [start, end] (the whole space by default)."""
 
+    _prefix = "abg_kn"
+
     def __init__(self, k: int, bits: int, levels: int = 1, seed: int = 0, start: int = 0, end: int = None, device: int = 0):
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
         self.k, self.bits, self.levels, self.seed = k, bits, levels, seed
         self.start, self.end = start, bits - 1 if end is None else end
-        rc = self._lib.abg_kn_create(device, bits, levels, k, seed, self.start, self.end, C.byref(self._h))
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_kn_last_error(None)
-            self._h = None
-            raise AbyssAmdError("abg_kn_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.abg_kn_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_kn_last_error(self._h)
-            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+        self._create(device, bits, levels, k, seed, self.start, self.end)
 
     @property
     def level_bytes(self) -> int:
@@ -599,46 +586,15 @@ class KonnectorBloom:
         head = b"5\n%d\n%d\t%d\t%d\n%d\n" % (self.k, self.bits, self.start, self.end, self.seed)
         return head + self.level(self.levels - 1).tobytes()
 
-    def profile(self, on: bool = True) -> None:
-        self._lib.abg_kn_profile(self._h, int(on))
-
-    def profile_get(self, name: str) -> Tuple[float, int]:
-        ms, n = C.c_double(), C.c_uint64()
-        self._lib.abg_kn_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
-        return ms.value, n.value
-
 
 FM_HIT = np.dtype([("l", "<u4"), ("u", "<u4"), ("qstart", "<u4"), ("qend", "<u4"), ("num", "<u4"), ("pos", "<u4")])
 
 
-class FMIndex:
+class FMIndex(_SwitchedHandle):
     """The FM-index of abyss-map and abyss-index on one GPU: the whole target file as text, alphabet -ACGT (FMIndex/FMIndex.h,
     Map/map.cc; include/abyss_amd.h abg_fm_*).  The occurrence table and the full suffix array stay in device memory."""
 
-    def __init__(self, device: int = 0):
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
-        rc = self._lib.abg_fm_create(device, C.byref(self._h))
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_fm_last_error(None)
-            self._h = None
-            raise AbyssAmdError("abg_fm_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.abg_fm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_fm_last_error(self._h)
-            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+    _prefix = "abg_fm"
 
     def build(self, text: bytes) -> None:
         """FMIndex::assign over the raw bytes of the target file."""
@@ -672,47 +628,16 @@ class FMIndex:
         """Search lanes = CUs x waves_per_cu x 64 (1..32; 0 restores the default)."""
         self._check(self._lib.abg_fm_tune(self._h, waves_per_cu), "abg_fm_tune")
 
-    def profile(self, on: bool = True) -> None:
-        self._lib.abg_fm_profile(self._h, int(on))
-
-    def profile_get(self, name: str) -> Tuple[float, int]:
-        ms, n = C.c_double(), C.c_uint64()
-        self._lib.abg_fm_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
-        return ms.value, n.value
-
 
 DE_JOB = np.dtype([("first", "<i4"), ("last", "<i4"), ("len0", "<u4"), ("len1", "<u4")])
 DE_PAIR = np.dtype([("first", "<i4"), ("last", "<i4"), ("len0", "<u4"), ("len1", "<u4"), ("l", "<u4"), ("rf", "<u4")])
 
 
-class DistanceMLE:
+class DistanceMLE(_SwitchedHandle):
     """DistanceEst's maximum-likelihood estimate on one GPU (DistanceEst/MLE.cpp; include/abyss_amd.h abg_de_*): the scan over
     theta on the device, every log and the O(thetas) tail on the host."""
 
-    def __init__(self, device: int = 0):
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
-        rc = self._lib.abg_de_create(device, C.byref(self._h))
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_de_last_error(None)
-            self._h = None
-            raise AbyssAmdError("abg_de_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.abg_de_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_de_last_error(self._h)
-            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+    _prefix = "abg_de"
 
     def set_pmf(self, pmf: np.ndarray, minp: float, mean: float) -> None:
         """PMF(h): its values, minProbability() and mean()."""
@@ -747,47 +672,16 @@ class DistanceMLE:
         """Thetas a workgroup: 64, 128, 192 or 256 (0 restores the default).  Changes no bit of any result."""
         self._check(self._lib.abg_de_tune(self._h, block_threads), "abg_de_tune")
 
-    def profile(self, on: bool = True) -> None:
-        self._lib.abg_de_profile(self._h, int(on))
-
-    def profile_get(self, name: str) -> Tuple[float, int]:
-        ms, n = C.c_double(), C.c_uint64()
-        self._lib.abg_de_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
-        return ms.value, n.value
-
 
 OV_PAIR = np.dtype([("t", "<u4"), ("h", "<u4")])
 
 
-class ContigOverlap:
+class ContigOverlap(_SwitchedHandle):
     """Overlap's suffix/prefix search on one GPU (Overlap/Overlap.cpp:151-198; include/abyss_amd.h abg_ov_*): for oriented contig
     pairs (t, h), the lengths l for which the last l bytes of t are the first l bytes of h.  A node is 2 * id + sense; sense set
     means the reverse complement."""
 
-    def __init__(self, device: int = 0):
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
-        rc = self._lib.abg_ov_create(device, C.byref(self._h))
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_ov_last_error(None)
-            self._h = None
-            raise AbyssAmdError("abg_ov_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.abg_ov_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_ov_last_error(self._h)
-            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+    _prefix = "abg_ov"
 
     def set_contigs(self, seqs) -> None:
         """The contigs, as bytes objects (or one uint8 array and its n + 1 offsets, as a tuple).  Case is folded to upper case here,
@@ -823,44 +717,13 @@ class ContigOverlap:
         lengths = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint32)), shape=(total,)).copy() if total else np.zeros(0, dtype=np.uint32)
         return lengths, off
 
-    def profile(self, on: bool = True) -> None:
-        self._lib.abg_ov_profile(self._h, int(on))
 
-    def profile_get(self, name: str) -> Tuple[float, int]:
-        ms, n = C.c_double(), C.c_uint64()
-        self._lib.abg_ov_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
-        return ms.value, n.value
-
-
-class PathSearch:
+class PathSearch(_SwitchedHandle):
     """SimpleGraph's constrained path search on one GPU (Graph/ConstrainedSearch.h:56-144; include/abyss_amd.h abg_sg_*): from an
     oriented vertex, every path through the graph on which each constraint vertex lies within its bound, in the order the reference's
     depth-first search finds them.  A vertex is 2 * id + sense."""
 
-    def __init__(self, device: int = 0):
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
-        rc = self._lib.abg_sg_create(device, C.byref(self._h))
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_sg_last_error(None)
-            self._h = None
-            raise AbyssAmdError("abg_sg_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.abg_sg_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_sg_last_error(self._h)
-            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+    _prefix = "abg_sg"
 
     def set_graph(self, edge_offsets, lengths, targets, distances) -> None:
         """The graph in CSR form: vertex u has length lengths[u] and the out-edges edge_offsets[u]:edge_offsets[u + 1] of targets and
@@ -903,40 +766,12 @@ class PathSearch:
         which slows it, so time without."""
         self._lib.abg_sg_profile(self._h, (2 if count_steps else 1) if on else 0)
 
-    def profile_get(self, name: str) -> Tuple[float, int]:
-        ms, n = C.c_double(), C.c_uint64()
-        self._lib.abg_sg_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
-        return ms.value, n.value
 
-
-class PathMerge:
+class PathMerge(_SwitchedHandle):
     """MergeContigs' sequence merge on one GPU (MergePaths/MergeContigs.cpp:159-313; include/abyss_amd.h abg_mc_*): paths of contigs
     spliced at their overlaps.  A node is 2 * id + sense, or -n for the gap of n bases."""
 
-    def __init__(self, device: int = 0):
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
-        rc = self._lib.abg_mc_create(device, C.byref(self._h))
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_mc_last_error(None)
-            self._h = None
-            raise AbyssAmdError("abg_mc_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.abg_mc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_mc_last_error(self._h)
-            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+    _prefix = "abg_mc"
 
     def set_contigs(self, contigs) -> None:
         """contigs: the sequences as bytes, case and IUPAC codes as they are to stay"""
@@ -970,59 +805,22 @@ class PathMerge:
         """bytes a splice tile (a multiple of 16) and paths a launch; 0 keeps a value"""
         self._check(self._lib.abg_mc_tune(self._h, tile, batch), "abg_mc_tune")
 
-    def profile(self, on: bool = True) -> None:
-        self._lib.abg_mc_profile(self._h, 1 if on else 0)
 
-    def profile_get(self, name: str) -> Tuple[float, int]:
-        ms, n = C.c_double(), C.c_uint64()
-        self._lib.abg_mc_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
-        return ms.value, n.value
-
-
-class BubbleAlign:
+class BubbleAlign(_TimedHandle):
     """PopBubbles' global alignment on one GPU (Align/alignGlobal.cc; include/abyss_amd.h abg_pb_*): for pairs of branches the number
     of matches, the length of the consensus and the consensus; for groups of three branches and more, alignMulti's chain."""
 
-    def __init__(self, device: int = 0):
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
-        rc = self._lib.abg_pb_create(device, C.byref(self._h))
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_pb_last_error(None)
-            self._h = None
-            raise AbyssAmdError("abg_pb_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
+    _prefix = "abg_pb"
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.abg_pb_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_pb_last_error(self._h)
-            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
-
-    @staticmethod
-    def _flat(seqs):
-        off = np.zeros(len(seqs) + 1, dtype=np.uint64)
-        if len(seqs):
-            np.cumsum([len(s) for s in seqs], out=off[1:])
-        data = np.frombuffer(b"".join(seqs), dtype=np.uint8) if int(off[-1]) else np.zeros(1, dtype=np.uint8)
-        return data, off
+    _flat = staticmethod(_flat)  # (an alias for callers that know it by this name)
 
     def align(self, pairs, consensus: bool = False):
         """pairs: [(a, b), ...] as bytes.  Returns (matches, size, redone) or, with consensus, (matches, size, redone, consensuses):
         alignGlobal's matches and consensus length of every pair, whether the host aligned it because its flags fit no arena, and
         the consensus strings as bytes."""
         n = len(pairs)
-        a, aoff = self._flat([p[0] for p in pairs])
-        b, boff = self._flat([p[1] for p in pairs])
+        a, aoff = _flat([p[0] for p in pairs])
+        b, boff = _flat([p[1] for p in pairs])
         matches, size, redone = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8)
         coff, cons = np.zeros(n + 1, dtype=np.uint64), C.c_void_p()
         self._check(self._lib.abg_pb_align(self._h, n, a.ctypes.data, aoff.ctypes.data, b.ctypes.data, boff.ctypes.data, 1 if consensus else 0,
@@ -1040,7 +838,7 @@ class BubbleAlign:
         first = np.zeros(n + 1, dtype=np.uint64)
         if n:
             np.cumsum([len(g) for g in groups], out=first[1:])
-        data, off = self._flat([s for g in groups for s in g])
+        data, off = _flat([s for g in groups for s in g])
         matches, size, redone = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8)
         coff, cons = np.zeros(n + 1, dtype=np.uint64), C.c_void_p()
         self._check(self._lib.abg_pb_align_chain(self._h, n, first.ctypes.data, data.ctypes.data, off.ctypes.data, matches.ctypes.data, size.ctypes.data,
@@ -1052,16 +850,8 @@ class BubbleAlign:
         """bytes of flags a launch may hold, the longest side a single lane takes (at most 32), pairs a launch; 0 keeps a value"""
         self._check(self._lib.abg_pb_tune(self._h, arena_bytes, small_limit, batch), "abg_pb_tune")
 
-    def profile_get(self, name: str) -> Tuple[float, int]:
-        ms, n = C.c_double(), C.c_uint64()
-        self._lib.abg_pb_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
-        return ms.value, n.value
 
-    def profile_reset(self) -> None:
-        self._lib.abg_pb_profile_reset(self._h)
-
-
-class PairMerge:
+class PairMerge(_TimedHandle):
     """abyss-mergepairs' overlap alignment on one GPU (Align/mergepairs.cc, Align/smith_waterman.cpp; include/abyss_amd.h abg_mp_*):
     for every pair of reads, how many overlaps of read 1 with the reverse complement of read 2 the reference keeps, how many pass
     each of its filters, and the one overlap to merge by when exactly one is left."""
@@ -1069,37 +859,14 @@ class PairMerge:
     FIELDS = ("n_aligned", "n_matches", "n_identity", "n_gapless", "t_pos", "h_pos", "length", "matches", "flags", "reserved")
     ORDER_DEPENDENT, HOST, BREAK_TAKEN, BREAK_NOT_TAKEN = 1, 2, 4, 8
 
-    def __init__(self, device: int = 0):
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
-        rc = self._lib.abg_mp_create(device, C.byref(self._h))
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_mp_last_error(None)
-            self._h = None
-            raise AbyssAmdError("abg_mp_create failed (%d): %s" % (rc, msg.decode() if msg else ""))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.abg_mp_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != _lib.ABG_OK:
-            msg = self._lib.abg_mp_last_error(self._h)
-            raise AbyssAmdError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+    _prefix = "abg_mp"
 
     def align(self, pairs, min_matches: int = 10, identity: float = 0.9):
         """pairs: [(read 1, read 2), ...] as bytes, as the files hold them.  Returns an (n, 10) array of uint32, a row a pair, its
         columns named by FIELDS."""
         n = len(pairs)
-        a, aoff = BubbleAlign._flat([p[0] for p in pairs])
-        b, boff = BubbleAlign._flat([p[1] for p in pairs])
+        a, aoff = _flat([p[0] for p in pairs])
+        b, boff = _flat([p[1] for p in pairs])
         records = np.zeros((n, len(self.FIELDS)), dtype=np.uint32)
         self._check(self._lib.abg_mp_align(self._h, n, a.ctypes.data, aoff.ctypes.data, b.ctypes.data, boff.ctypes.data, min_matches, identity,
                                            records.ctypes.data), "abg_mp_align")
@@ -1108,11 +875,3 @@ class PairMerge:
     def tune(self, max_len: int = 0, spill_bytes: int = 0, batch: int = 0) -> None:
         """the longest read the kernel takes (at most 512), bytes of spilled rows a launch may hold, pairs a launch; 0 keeps a value"""
         self._check(self._lib.abg_mp_tune(self._h, max_len, spill_bytes, batch), "abg_mp_tune")
-
-    def profile_get(self, name: str) -> Tuple[float, int]:
-        ms, n = C.c_double(), C.c_uint64()
-        self._lib.abg_mp_profile_get(self._h, name.encode(), C.byref(ms), C.byref(n))
-        return ms.value, n.value
-
-    def profile_reset(self) -> None:
-        self._lib.abg_mp_profile_reset(self._h)

@@ -53,15 +53,15 @@ OBJ_DIR = os.path.join(ROOT, "abyss_amd", "lib", "obj")
 # translation units of the library and what each is rebuilt for (the big one takes minutes; the others seconds)
 UNITS = {
     "abg_kernels": ["abg_kernels.hip", "abg_core.h", "abg_engine.h", "abg_walk.h", "abg_host.h", "abg_overlap.h"],
-    "abg_rr": ["abg_rr.hip", "abg_rr.h", "abg_core.h"],
-    "abg_kn": ["abg_kn.hip", "abg_kn.h", "abg_core.h"],
-    "abg_fm": ["abg_fm.hip", "abg_fm.h", "abg_core.h"],
-    "abg_de": ["abg_de.hip", "abg_de.h", "abg_core.h"],
-    "abg_ov": ["abg_ov.hip", "abg_ov.h", "abg_core.h"],
-    "abg_sg": ["abg_sg.hip", "abg_sg.h", "abg_core.h"],
-    "abg_mc": ["abg_mc.hip", "abg_mc.h", "abg_ov.h", "abg_core.h"],
-    "abg_pb": ["abg_pb.hip", "abg_pb.h", "abg_mc.h", "abg_ov.h", "abg_core.h"],
-    "abg_mp": ["abg_mp.hip", "abg_mp.h", "abg_mc.h", "abg_ov.h", "abg_core.h"],
+    "abg_rr": ["abg_rr.hip", "abg_rr.h", "abg_stage.h", "abg_core.h"],
+    "abg_kn": ["abg_kn.hip", "abg_kn.h", "abg_stage.h", "abg_core.h"],
+    "abg_fm": ["abg_fm.hip", "abg_fm.h", "abg_stage.h", "abg_core.h"],
+    "abg_de": ["abg_de.hip", "abg_de.h", "abg_stage.h", "abg_core.h"],
+    "abg_ov": ["abg_ov.hip", "abg_ov.h", "abg_stage.h", "abg_core.h"],
+    "abg_sg": ["abg_sg.hip", "abg_sg.h", "abg_stage.h", "abg_core.h"],
+    "abg_mc": ["abg_mc.hip", "abg_mc.h", "abg_stage.h", "abg_ov.h", "abg_core.h"],
+    "abg_pb": ["abg_pb.hip", "abg_pb.h", "abg_stage.h", "abg_mc.h", "abg_ov.h", "abg_core.h"],
+    "abg_mp": ["abg_mp.hip", "abg_mp.h", "abg_stage.h", "abg_mc.h", "abg_ov.h", "abg_core.h"],
 }
 # flags a unit adds to the common command line (abg_de: its sums must match a serial evaluation bit for bit, so no product may be
 # fused into an add, on the device or in the host tail)
@@ -90,34 +90,36 @@ def build_lib(force: bool = False) -> str:
     return LIB
 
 
+# the host binaries over the C ABI: (binary, its main under csrc/host, flags it adds to the common command line)
+CLI = [
+    ("abyss-bloom-dbg", "bloom_dbg_main.cc", []),
+    ("abyss-bloom", "bloom_main.cc", []),
+    ("AdjList", "adjlist_main.cc", []),
+    ("abyss-rresolver-short", "rresolver_main.cc", []),
+    ("abyss-map", "map_main.cc", []),
+    ("abyss-index", "index_main.cc", []),
+    ("DistanceEst", "distanceest_main.cc", ["-ffp-contract=off"]),  # (its host tail adds up as the reference's does, see UNIT_FLAGS)
+    ("Overlap", "overlap_main.cc", []),
+    ("SimpleGraph", "simplegraph_main.cc", []),
+    ("MergeContigs", "mergecontigs_main.cc", []),
+    ("PopBubbles", "popbubbles_main.cc", []),
+    ("abyss-mergepairs", "mergepairs_main.cc", []),
+]
+
+
 def build_cli(force: bool = False) -> str:
-    """abyss_amd/bin/abyss-bloom-dbg: the drop-in host binary (C++ over the C ABI)."""
-    src = os.path.join(CSRC, "host", "bloom_dbg_main.cc")
-    out = os.path.join(BIN_DIR, "abyss-bloom-dbg")
-    if not os.path.exists(src):
+    """abyss_amd/bin/abyss-bloom-dbg and the other drop-in host binaries (C++ over the C ABI)."""
+    host = os.path.join(CSRC, "host")
+    out = os.path.join(BIN_DIR, CLI[0][0])
+    if not os.path.exists(os.path.join(host, CLI[0][1])):
         return ""
-    deps = [src] + [os.path.join(CSRC, "host", f) for f in os.listdir(os.path.join(CSRC, "host"))]
+    deps = [os.path.join(host, f) for f in os.listdir(host)]
     if force or _newer(out, deps + [LIB]):
         os.makedirs(BIN_DIR, exist_ok=True)
         build_lib()
-        _run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-o", out, src,
-              "-L" + os.path.dirname(LIB), "-labyss_amd", "-Wl,-rpath,$ORIGIN/../lib", "-lpthread"])
-        _run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-o",
-              os.path.join(BIN_DIR, "abyss-bloom"), os.path.join(CSRC, "host", "bloom_main.cc"),
-              "-L" + os.path.dirname(LIB), "-labyss_amd", "-Wl,-rpath,$ORIGIN/../lib", "-lpthread"])
-        _run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-o",
-              os.path.join(BIN_DIR, "AdjList"), os.path.join(CSRC, "host", "adjlist_main.cc"),
-              "-L" + os.path.dirname(LIB), "-labyss_amd", "-Wl,-rpath,$ORIGIN/../lib", "-lpthread"])
-        _run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-o",
-              os.path.join(BIN_DIR, "abyss-rresolver-short"), os.path.join(CSRC, "host", "rresolver_main.cc"),
-              "-L" + os.path.dirname(LIB), "-labyss_amd", "-Wl,-rpath,$ORIGIN/../lib", "-lpthread"])
-        for name, main in (("abyss-map", "map_main.cc"), ("abyss-index", "index_main.cc"), ("DistanceEst", "distanceest_main.cc"),
-                           ("Overlap", "overlap_main.cc"), ("SimpleGraph", "simplegraph_main.cc"), ("MergeContigs", "mergecontigs_main.cc"),
-                           ("PopBubbles", "popbubbles_main.cc"), ("abyss-mergepairs", "mergepairs_main.cc")):
-            _run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-o",
-                  os.path.join(BIN_DIR, name), os.path.join(CSRC, "host", main),
-                  "-L" + os.path.dirname(LIB), "-labyss_amd", "-Wl,-rpath,$ORIGIN/../lib", "-lpthread"] +
-                 (["-ffp-contract=off"] if name == "DistanceEst" else []))
+        for name, main, extra in CLI:
+            _run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "include"), "-o", os.path.join(BIN_DIR, name),
+                  os.path.join(host, main), "-L" + os.path.dirname(LIB), "-labyss_amd", "-Wl,-rpath,$ORIGIN/../lib", "-lpthread"] + extra)
     return out
 
 
@@ -131,75 +133,44 @@ def build_oracle(force: bool = False) -> None:
     _run(["make", "-C", ORACLE_DIR, "-j8"] + targets)
 
 
-READER_CHECK = os.path.join(ROOT, "tests", "hostcheck", "reader_check")
-ADJLIST_CHECK = os.path.join(ROOT, "tests", "hostcheck", "adjlist_check")
-RRESOLVER_CHECK = os.path.join(ROOT, "tests", "hostcheck", "rresolver_check")
-KN_CHECK = os.path.join(ROOT, "tests", "hostcheck", "kn_check")
-FM_CHECK = os.path.join(ROOT, "tests", "hostcheck", "fm_check")
-DE_CHECK = os.path.join(ROOT, "tests", "hostcheck", "de_check")
-OV_CHECK = os.path.join(ROOT, "tests", "hostcheck", "ov_check")
-SG_CHECK = os.path.join(ROOT, "tests", "hostcheck", "sg_check")
-MC_CHECK = os.path.join(ROOT, "tests", "hostcheck", "mc_check")
-PB_CHECK = os.path.join(ROOT, "tests", "hostcheck", "pb_check")
-MP_CHECK = os.path.join(ROOT, "tests", "hostcheck", "mp_check")
+HOSTCHECK_DIR = os.path.join(ROOT, "tests", "hostcheck")
+_GRAPH_HOST = ["rresolver_core.h", "graph_writers.h", "fasta_reader.h", "si_bytes.h"]
+# the stand-alone checkers: (constant, source under tests/hostcheck, what else it is rebuilt for under csrc, flags between -O2 and -o,
+# flags after the source)
+CHECKERS = [
+    ("READER_CHECK", "reader_check.cc", ["host/fasta_reader.h"], [], []),
+    ("ADJLIST_CHECK", "adjlist_check.cc", ["host/adjlist_core.h", "host/fasta_reader.h"], [],
+     ["-L" + HOSTCHECK_DIR, "-lhostcheck", "-Wl,-rpath,$ORIGIN"]),
+    ("RRESOLVER_CHECK", "rresolver_check.cc", ["abg_rr.h", "abg_core.h"] + ["host/" + f for f in _GRAPH_HOST], ["-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("KN_CHECK", "kn_check.cc", ["abg_kn.h", "abg_core.h", "host/bloom_core.h", "host/fasta_reader.h"], ["-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("FM_CHECK", "fm_check.cc", ["abg_fm.h", "abg_core.h", "host/map_core.h", "host/fasta_reader.h"], ["-Wno-unknown-pragmas"], ["-lpthread"]),
+    # (no -march and no contraction: its sums are the reference's, bit for bit)
+    ("DE_CHECK", "de_check.cc", ["abg_de.h", "abg_core.h", "host/distanceest_core.h"], ["-ffp-contract=off", "-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("OV_CHECK", "ov_check.cc", ["abg_ov.h", "abg_core.h", "host/overlap_core.h"] + ["host/" + f for f in _GRAPH_HOST],
+     ["-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("SG_CHECK", "sg_check.cc", ["abg_sg.h", "abg_core.h", "host/simplegraph_core.h", "host/overlap_core.h"] + ["host/" + f for f in _GRAPH_HOST],
+     ["-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("MC_CHECK", "mc_check.cc", ["abg_mc.h", "abg_ov.h", "abg_core.h", "host/mergecontigs_core.h", "host/overlap_core.h"] + ["host/" + f for f in _GRAPH_HOST],
+     ["-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("PB_CHECK", "pb_check.cc", ["abg_pb.h", "abg_mc.h", "abg_ov.h", "abg_core.h", "host/popbubbles_core.h"] + ["host/" + f for f in _GRAPH_HOST],
+     ["-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("MP_CHECK", "mp_check.cc", ["abg_mp.h", "abg_mc.h", "abg_ov.h", "abg_core.h", "host/mergepairs_core.h", "host/fasta_reader.h"],
+     ["-Wno-unknown-pragmas"], ["-lpthread"]),
+]
+for _name, _src, _deps, _flags, _libs in CHECKERS:  # READER_CHECK = .../tests/hostcheck/reader_check, and so on
+    globals()[_name] = os.path.join(HOSTCHECK_DIR, _src[:-len(".cc")])
 
 
 def build_hostcheck(force: bool = False) -> str:
     # (hostcheck_ext.cc includes hostcheck.cc and adds the entry points written after it)
-    src = os.path.join(ROOT, "tests", "hostcheck", "hostcheck_ext.cc")
-    if force or _newer(HOSTCHECK, [src, os.path.join(ROOT, "tests", "hostcheck", "hostcheck.cc")] + csrc_files()):
+    src = os.path.join(HOSTCHECK_DIR, "hostcheck_ext.cc")
+    if force or _newer(HOSTCHECK, [src, os.path.join(HOSTCHECK_DIR, "hostcheck.cc")] + csrc_files()):
         _run(["g++", "-std=c++17", "-O2", "-g", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-o", HOSTCHECK, src])
-    rsrc = os.path.join(ROOT, "tests", "hostcheck", "reader_check.cc")
-    if force or _newer(READER_CHECK, [rsrc, os.path.join(CSRC, "host", "fasta_reader.h")]):
-        _run(["g++", "-std=c++17", "-O2", "-o", READER_CHECK, rsrc])
-    asrc = os.path.join(ROOT, "tests", "hostcheck", "adjlist_check.cc")
-    if force or _newer(ADJLIST_CHECK, [asrc, HOSTCHECK, os.path.join(CSRC, "host", "adjlist_core.h"),
-                                       os.path.join(CSRC, "host", "fasta_reader.h")]):
-        _run(["g++", "-std=c++17", "-O2", "-o", ADJLIST_CHECK, asrc, "-L" + os.path.dirname(HOSTCHECK), "-lhostcheck",
-              "-Wl,-rpath,$ORIGIN"])
-    hsrc = [os.path.join(CSRC, "host", f) for f in ("rresolver_core.h", "graph_writers.h", "fasta_reader.h", "si_bytes.h")]
-    csrc = os.path.join(ROOT, "tests", "hostcheck", "rresolver_check.cc")
-    if force or _newer(RRESOLVER_CHECK, [csrc, os.path.join(CSRC, "abg_rr.h"), os.path.join(CSRC, "abg_core.h")] + hsrc):
-        _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", RRESOLVER_CHECK, csrc, "-lpthread"])
-    ksrc = os.path.join(ROOT, "tests", "hostcheck", "kn_check.cc")
-    kdeps = [ksrc] + [os.path.join(CSRC, f) for f in ("abg_kn.h", "abg_core.h")] + \
-        [os.path.join(CSRC, "host", f) for f in ("bloom_core.h", "fasta_reader.h")]
-    if force or _newer(KN_CHECK, kdeps):
-        _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", KN_CHECK, ksrc, "-lpthread"])
-    fsrc = os.path.join(ROOT, "tests", "hostcheck", "fm_check.cc")
-    fdeps = [fsrc] + [os.path.join(CSRC, f) for f in ("abg_fm.h", "abg_core.h")] + \
-        [os.path.join(CSRC, "host", f) for f in ("map_core.h", "fasta_reader.h")]
-    if force or _newer(FM_CHECK, fdeps):
-        _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", FM_CHECK, fsrc, "-lpthread"])
-    dsrc = os.path.join(ROOT, "tests", "hostcheck", "de_check.cc")
-    ddeps = [dsrc] + [os.path.join(CSRC, f) for f in ("abg_de.h", "abg_core.h")] + [os.path.join(CSRC, "host", "distanceest_core.h")]
-    if force or _newer(DE_CHECK, ddeps):  # (no -march and no contraction: its sums are the reference's, bit for bit)
-        _run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wno-unknown-pragmas", "-o", DE_CHECK, dsrc, "-lpthread"])
-    osrc = os.path.join(ROOT, "tests", "hostcheck", "ov_check.cc")
-    odeps = [osrc] + [os.path.join(CSRC, f) for f in ("abg_ov.h", "abg_core.h")] + \
-        [os.path.join(CSRC, "host", f) for f in ("overlap_core.h", "rresolver_core.h", "graph_writers.h", "fasta_reader.h", "si_bytes.h")]
-    if force or _newer(OV_CHECK, odeps):
-        _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", OV_CHECK, osrc, "-lpthread"])
-    ssrc = os.path.join(ROOT, "tests", "hostcheck", "sg_check.cc")
-    sdeps = [ssrc] + [os.path.join(CSRC, f) for f in ("abg_sg.h", "abg_core.h")] + \
-        [os.path.join(CSRC, "host", f) for f in ("simplegraph_core.h", "overlap_core.h", "rresolver_core.h", "graph_writers.h", "fasta_reader.h", "si_bytes.h")]
-    if force or _newer(SG_CHECK, sdeps):
-        _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", SG_CHECK, ssrc, "-lpthread"])
-    msrc = os.path.join(ROOT, "tests", "hostcheck", "mc_check.cc")
-    mdeps = [msrc] + [os.path.join(CSRC, f) for f in ("abg_mc.h", "abg_ov.h", "abg_core.h")] + \
-        [os.path.join(CSRC, "host", f) for f in ("mergecontigs_core.h", "overlap_core.h", "rresolver_core.h", "graph_writers.h", "fasta_reader.h", "si_bytes.h")]
-    if force or _newer(MC_CHECK, mdeps):
-        _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", MC_CHECK, msrc, "-lpthread"])
-    psrc = os.path.join(ROOT, "tests", "hostcheck", "pb_check.cc")
-    pdeps = [psrc] + [os.path.join(CSRC, f) for f in ("abg_pb.h", "abg_mc.h", "abg_ov.h", "abg_core.h")] + \
-        [os.path.join(CSRC, "host", f) for f in ("popbubbles_core.h", "rresolver_core.h", "graph_writers.h", "fasta_reader.h", "si_bytes.h")]
-    if force or _newer(PB_CHECK, pdeps):
-        _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", PB_CHECK, psrc, "-lpthread"])
-    qsrc = os.path.join(ROOT, "tests", "hostcheck", "mp_check.cc")
-    qdeps = [qsrc] + [os.path.join(CSRC, f) for f in ("abg_mp.h", "abg_mc.h", "abg_ov.h", "abg_core.h")] + \
-        [os.path.join(CSRC, "host", f) for f in ("mergepairs_core.h", "fasta_reader.h")]
-    if force or _newer(MP_CHECK, qdeps):
-        _run(["g++", "-std=c++17", "-O2", "-Wno-unknown-pragmas", "-o", MP_CHECK, qsrc, "-lpthread"])
+    for name, source, deps, flags, libs in CHECKERS:
+        out, src = globals()[name], os.path.join(HOSTCHECK_DIR, source)
+        # (adjlist_check links libhostcheck.so, so it is rebuilt after it)
+        if force or _newer(out, [src] + [os.path.join(CSRC, d) for d in deps] + ([HOSTCHECK] if "-lhostcheck" in libs else [])):
+            _run(["g++", "-std=c++17", "-O2"] + flags + ["-o", out, src] + libs)
     return HOSTCHECK
 
 

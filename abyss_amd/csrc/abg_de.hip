@@ -14,13 +14,15 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/abyss_amd.h"
 #include "abg_de.h"
+#include "abg_stage.h"
+
+namespace st = abg::stage;
 
 static_assert(sizeof(abg_de_job) == sizeof(abg::DEJob) && sizeof(abg_de_pair) == sizeof(abg::DEPair), "ABI structs");
 
@@ -63,8 +65,6 @@ __global__ __launch_bounds__(abg::DE_BLOCK) void de_scan_kernel(const abg::DEJob
 	}
 }
 
-struct Prof { double ms = 0; uint64_t launches = 0; };
-
 uint64_t align16(uint64_t x) { return (x + 15) & ~15ull; }
 
 // one batch in flight: its inputs (pinned and on the device), its results (on the device and pinned)
@@ -87,15 +87,14 @@ struct abg_de {
 	uint32_t block = abg::DE_BLOCK;
 	Slot slot[2];
 	bool profiling = false;
-	std::map<std::string, Prof> prof;
-	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
+	st::Profile prof;
 	uint64_t terms = 0; // PMF entries x thetas of the profiled calls
 	std::string error;
 	~abg_de()
 	{
 		(void)hipSetDevice(device);
 		if (stream) (void)hipStreamSynchronize(stream);
-		for (auto& e : pending) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
+		prof.drop();
 		for (Slot& s : slot) {
 			if (s.hin) (void)hipHostFree(s.hin);
 			if (s.din) (void)hipFree(s.din);
@@ -112,38 +111,6 @@ struct abg_de {
 namespace {
 
 std::string g_de_create_error;
-
-int de_fail(abg_de* d, hipError_t e, const char* what)
-{
-	(void)hipGetLastError();
-	d->error = std::string(what) + " failed: " + hipGetErrorString(e);
-	return e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL;
-}
-
-void prof_drain(abg_de* d)
-{
-	for (auto& e : d->pending) {
-		float ms = 0;
-		(void)hipEventSynchronize(e.second.second);
-		if (hipEventElapsedTime(&ms, e.second.first, e.second.second) == hipSuccess) { d->prof[e.first].ms += ms; d->prof[e.first].launches++; }
-		(void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second);
-	}
-	d->pending.clear();
-}
-
-hipError_t grow(void** host, void** dev, size_t* cap, size_t need)
-{
-	if (need <= *cap) return hipSuccess;
-	if (*host) (void)hipHostFree(*host);
-	if (*dev) (void)hipFree(*dev);
-	*host = *dev = nullptr;
-	*cap = 0;
-	need += need / 4 + 4096;
-	hipError_t e = hipHostMalloc(host, need);
-	if (e == hipSuccess) e = hipMalloc(dev, need);
-	if (e == hipSuccess) *cap = need;
-	return e;
-}
 
 // Queues jobs [a, b) on slot s: inputs up, the kernel, results down into the slot's pinned buffer, the slot's event.
 // The slot must be idle.  soff: the caller's sample offsets (njobs + 1).
@@ -164,9 +131,9 @@ int launch_batch(abg_de* d, Slot& s, const abg::DEJob* jobs, uint64_t a, uint64_
 	               o_soff = align16(o_toff + (nj + 1) * 8), o_sv = align16(o_soff + (nj + 1) * 8), o_sc = align16(o_sv + ns * 4),
 	               in_bytes = align16(o_sc + ns * 4);
 	const uint64_t o_c = 0, o_l = thetas * 8, o_n = thetas * 16, out_bytes = thetas * 20;
-	hipError_t e = grow(&s.hin, &s.din, &s.in_cap, in_bytes);
-	if (e == hipSuccess) e = grow(&s.hout, &s.dout, &s.out_cap, out_bytes);
-	if (e != hipSuccess) return de_fail(d, e, "allocating a batch");
+	hipError_t e = st::grow_pinned_slack(&s.hin, &s.din, &s.in_cap, in_bytes);
+	if (e == hipSuccess) e = st::grow_pinned_slack(&s.hout, &s.dout, &s.out_cap, out_bytes);
+	if (e != hipSuccess) return st::fail(d->error, e, "allocating a batch");
 	char* h = (char*)s.hin;
 	memcpy(h + o_jobs, jobs + a, nj * sizeof(abg::DEJob));
 	uint2* blocks = (uint2*)(h + o_blocks);
@@ -186,25 +153,22 @@ int launch_batch(abg_de* d, Slot& s, const abg::DEJob* jobs, uint64_t a, uint64_
 	memcpy(h + o_sv, sv + soff[a], ns * 4);
 	memcpy(h + o_sc, sc + soff[a], ns * 4);
 	e = hipMemcpyAsync(s.din, s.hin, in_bytes, hipMemcpyHostToDevice, d->stream);
-	if (e != hipSuccess) return de_fail(d, e, "copying a batch to the device");
-	hipEvent_t pa = nullptr, pb = nullptr;
-	if (d->profiling) {
-		(void)hipEventCreate(&pa); (void)hipEventCreate(&pb);
-		(void)hipEventRecord(pa, d->stream);
-		d->terms += thetas * (uint64_t)d->npmf;
-	}
+	if (e != hipSuccess) return st::fail(d->error, e, "copying a batch to the device");
+	if (d->profiling) d->terms += thetas * (uint64_t)d->npmf;
 	char* dv = (char*)s.din;
 	char* dw = (char*)s.dout;
-	hipLaunchKernelGGL(de_scan_kernel, dim3((unsigned)nblocks), dim3(d->block), 0, d->stream, (const abg::DEJob*)(dv + o_jobs),
-	    (const uint2*)(dv + o_blocks), (const uint64_t*)(dv + o_toff), (const uint64_t*)(dv + o_soff), (const int32_t*)(dv + o_sv),
-	    (const uint32_t*)(dv + o_sc), d->pmf, d->logp, d->npmf, d->minp, d->logminp, (double*)(dw + o_c), (double*)(dw + o_l),
-	    (uint32_t*)(dw + o_n));
-	e = hipGetLastError();
-	if (pa) { (void)hipEventRecord(pb, d->stream); d->pending.push_back({ "de_scan", { pa, pb } }); }
-	if (e != hipSuccess) return de_fail(d, e, "launching the scan");
+	{
+		st::Timed t(d->prof, d->stream, "de_scan", d->profiling);
+		hipLaunchKernelGGL(de_scan_kernel, dim3((unsigned)nblocks), dim3(d->block), 0, d->stream, (const abg::DEJob*)(dv + o_jobs),
+		    (const uint2*)(dv + o_blocks), (const uint64_t*)(dv + o_toff), (const uint64_t*)(dv + o_soff), (const int32_t*)(dv + o_sv),
+		    (const uint32_t*)(dv + o_sc), d->pmf, d->logp, d->npmf, d->minp, d->logminp, (double*)(dw + o_c), (double*)(dw + o_l),
+		    (uint32_t*)(dw + o_n));
+		e = hipGetLastError();
+	}
+	if (e != hipSuccess) return st::fail(d->error, e, "launching the scan");
 	e = hipMemcpyAsync(s.hout, s.dout, out_bytes, hipMemcpyDeviceToHost, d->stream);
 	if (e == hipSuccess) e = hipEventRecord(s.done, d->stream);
-	if (e != hipSuccess) return de_fail(d, e, "copying a batch's results");
+	if (e != hipSuccess) return st::fail(d->error, e, "copying a batch's results");
 	return ABG_OK;
 }
 
@@ -212,7 +176,7 @@ int wait_batch(abg_de* d, Slot& s)
 {
 	if (s.thetas == 0) return ABG_OK;
 	const hipError_t e = hipEventSynchronize(s.done);
-	return e == hipSuccess ? ABG_OK : de_fail(d, e, "the scan");
+	return e == hipSuccess ? ABG_OK : st::fail(d->error, e, "the scan");
 }
 
 // where batches end: whole jobs, at most batch_thetas thetas unless one job alone has more
@@ -256,21 +220,19 @@ int abg_de_create(int device, abg_de** out)
 {
 	if (!out) return ABG_EINVAL;
 	*out = nullptr;
-	int n = 0;
-	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); g_de_create_error = "no HIP device available (abyss_amd has no CPU fallback)"; return ABG_ENODEV; }
-	if (device < 0 || device >= n) { g_de_create_error = "HIP device ordinal out of range"; return ABG_ENODEV; }
+	hipStream_t stream = nullptr;
+	const int rc = st::open_device(device, "distance estimator", g_de_create_error, &stream, 1);
+	if (rc != ABG_OK) return rc;
 	abg_de* d = new abg_de;
 	d->device = device;
-	hipError_t e = hipSetDevice(device);
-	if (e == hipSuccess) e = hipStreamCreate(&d->stream);
+	d->stream = stream;
+	hipError_t e = hipSuccess;
 	for (Slot& s : d->slot)
 		if (e == hipSuccess) e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
 	if (e != hipSuccess) {
-		(void)hipGetLastError();
-		g_de_create_error = std::string("creating the distance estimator failed: ") + hipGetErrorString(e);
-		const int rc = e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL;
+		const int failed = st::create_fail(g_de_create_error, e, "distance estimator");
 		delete d;
-		return rc;
+		return failed;
 	}
 	if (const char* v = getenv("ABG_DE_BATCH_THETAS")) {
 		const unsigned long long t = strtoull(v, nullptr, 10);
@@ -299,7 +261,7 @@ int abg_de_set_pmf(abg_de* d, const double* pmf, uint64_t n, double minp, double
 	if (e == hipSuccess) e = hipMalloc((void**)&d->logp, n * 8);
 	if (e == hipSuccess) e = hipMemcpy(d->pmf, pmf, n * 8, hipMemcpyHostToDevice);
 	if (e == hipSuccess) e = hipMemcpy(d->logp, lp.data(), n * 8, hipMemcpyHostToDevice);
-	if (e != hipSuccess) return de_fail(d, e, "uploading the PMF");
+	if (e != hipSuccess) return st::fail(d->error, e, "uploading the PMF");
 	d->npmf = (int)n;
 	d->minp = minp;
 	d->logminp = log(minp);
@@ -432,16 +394,12 @@ int abg_de_profile_get(abg_de* d, const char* name, double* total_ms, uint64_t* 
 {
 	if (!d || !name) return ABG_EINVAL;
 	(void)hipSetDevice(d->device);
-	prof_drain(d);
 	if (!strcmp(name, "de_scan_terms")) { // not a kernel: PMF entries x thetas of the profiled calls, as `launches`
 		if (total_ms) *total_ms = 0;
 		if (launches) *launches = d->terms;
 		return ABG_OK;
 	}
-	auto it = d->prof.find(name);
-	if (total_ms) *total_ms = it == d->prof.end() ? 0 : it->second.ms;
-	if (launches) *launches = it == d->prof.end() ? 0 : it->second.launches;
-	return ABG_OK;
+	return d->prof.get(name, total_ms, launches);
 }
 
 } // extern "C"

@@ -19,12 +19,14 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/abyss_amd.h"
 #include "abg_fm.h"
+#include "abg_stage.h"
+
+namespace st = abg::stage;
 
 static_assert(sizeof(abg_fm_hit) == sizeof(abg::FMHit), "abg_fm_hit and abg::FMHit are one layout");
 
@@ -153,8 +155,6 @@ __global__ void __launch_bounds__(256) k_fm_map(abg::FMView v, const uint32_t* _
 	}
 }
 
-struct Prof { double ms = 0; uint64_t launches = 0; };
-
 } // namespace
 
 struct abg_fm {
@@ -171,8 +171,7 @@ struct abg_fm {
 	uint64_t steps = 0;
 	uint32_t cus = 256, waves = abg::FM_WAVES_PER_CU;
 	bool profiling = false;
-	std::map<std::string, Prof> prof;
-	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
+	st::Profile prof;
 	std::string error;
 	void drop_index()
 	{
@@ -185,7 +184,7 @@ struct abg_fm {
 	{
 		(void)hipSetDevice(device);
 		if (stream) (void)hipStreamSynchronize(stream);
-		for (auto& e : pending) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
+		prof.drop();
 		drop_index();
 		if (qdev) (void)hipFree(qdev);
 		if (memo) (void)hipFree(memo);
@@ -197,41 +196,6 @@ struct abg_fm {
 namespace {
 
 std::string g_fm_create_error;
-
-bool fm_ok(abg_fm* f, hipError_t e, const char* what)
-{
-	if (e == hipSuccess) return true;
-	(void)hipGetLastError();
-	f->error = std::string(what) + " failed: " + hipGetErrorString(e);
-	return false;
-}
-int fm_code_of(hipError_t e) { return e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL; }
-
-struct Timed { // brackets a piece of stream work with events when profiling
-	abg_fm* f; const char* name; hipEvent_t a = nullptr, b = nullptr;
-	Timed(abg_fm* f, const char* name) : f(f), name(name)
-	{
-		if (!f->profiling) return;
-		(void)hipEventCreate(&a); (void)hipEventCreate(&b);
-		(void)hipEventRecord(a, f->stream);
-	}
-	~Timed()
-	{
-		if (!a) return;
-		(void)hipEventRecord(b, f->stream);
-		f->pending.push_back({ name, { a, b } });
-	}
-};
-void prof_drain(abg_fm* f)
-{
-	for (auto& e : f->pending) {
-		float ms = 0;
-		(void)hipEventSynchronize(e.second.second);
-		if (hipEventElapsedTime(&ms, e.second.first, e.second.second) == hipSuccess) { f->prof[e.first].ms += ms; f->prof[e.first].launches++; }
-		(void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second);
-	}
-	f->pending.clear();
-}
 
 // device buffers of one build, freed when it ends
 struct Scratch {
@@ -247,7 +211,7 @@ struct Scratch {
 
 struct MaxOp { __host__ __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; } };
 
-#define FM_TRY(expr, what) do { const hipError_t e_ = (expr); if (!fm_ok(f, e_, what)) return fm_code_of(e_); } while (0)
+#define FM_TRY(expr, what) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return st::fail(f->error, e_, what); } while (0)
 
 int build_index(abg_fm* f, const uint8_t* text, uint64_t n64)
 {
@@ -286,7 +250,7 @@ int build_index(abg_fm* f, const uint8_t* text, uint64_t n64)
 	while (bits < 32 && (1ull << bits) <= (uint64_t)n + 1) bits++; // ranks are 1..n, 0 past the end
 
 	{
-		Timed tm(f, "fm_sa");
+		st::Timed tm(f->prof, f->stream, "fm_sa", f->profiling);
 		FM_TRY(hipMemcpyAsync(t, text, n, hipMemcpyHostToDevice, st), "copying the text to the device");
 		k_fm_encode<<<grid, 256, 0, st>>>(t, n);
 		k_fm_key_first<<<grid, 256, 0, st>>>(t, n, key_a, idx_a);
@@ -312,7 +276,7 @@ int build_index(abg_fm* f, const uint8_t* text, uint64_t n64)
 		}
 	}
 	{
-		Timed tm(f, "fm_occ");
+		st::Timed tm(f->prof, f->stream, "fm_occ", f->profiling);
 		k_fm_bwt<<<grid_m, 256, 0, st>>>(t, idx_b, n, f->sa, f->bwt, small + 1);
 		k_fm_occ_fill<<<grid_b, 256, 0, st>>>(f->bwt, m, nb, f->occ, local);
 		FM_TRY(hipGetLastError(), "the table kernel launch");
@@ -345,20 +309,17 @@ int abg_fm_create(int device, abg_fm** out)
 {
 	if (!out) return ABG_EINVAL;
 	*out = nullptr;
-	int n = 0;
-	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); g_fm_create_error = "no HIP device available (abyss_amd has no CPU fallback)"; return ABG_ENODEV; }
-	if (device < 0 || device >= n) { g_fm_create_error = "HIP device ordinal out of range"; return ABG_ENODEV; }
+	hipStream_t stream = nullptr;
+	const int opened = st::open_device(device, "FM-index", g_fm_create_error, &stream, 1);
+	if (opened != ABG_OK) return opened;
 	abg_fm* f = new abg_fm;
 	f->device = device;
-	hipError_t e = hipSetDevice(device);
+	f->stream = stream;
 	hipDeviceProp_t prop;
-	if (e == hipSuccess && hipGetDeviceProperties(&prop, device) == hipSuccess) f->cus = (uint32_t)prop.multiProcessorCount;
-	if (e == hipSuccess) e = hipStreamCreate(&f->stream);
-	if (e == hipSuccess) e = hipMalloc((void**)&f->ticket, 16);
+	if (hipGetDeviceProperties(&prop, device) == hipSuccess) f->cus = (uint32_t)prop.multiProcessorCount;
+	hipError_t e = hipMalloc((void**)&f->ticket, 16);
 	if (e != hipSuccess) {
-		(void)hipGetLastError();
-		g_fm_create_error = std::string("creating the FM-index failed: ") + hipGetErrorString(e);
-		const int rc = fm_code_of(e);
+		const int rc = st::create_fail(g_fm_create_error, e, "FM-index");
 		delete f;
 		return rc;
 	}
@@ -399,7 +360,7 @@ int abg_fm_export(abg_fm* f, uint32_t* sa, uint8_t* bwt)
 	if (sa) e = hipMemcpyAsync(sa, f->sa, m * 4, hipMemcpyDeviceToHost, f->stream);
 	if (e == hipSuccess && bwt) e = hipMemcpyAsync(bwt, f->bwt, m, hipMemcpyDeviceToHost, f->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
-	if (!fm_ok(f, e, "copying the index to the host")) return fm_code_of(e);
+	if (e != hipSuccess) return st::fail(f->error, e, "copying the index to the host");
 	if (bwt) for (uint64_t i = 0; i < m; i++) if (bwt[i] == abg::FM_SENT) bwt[i] = 255;
 	return ABG_OK;
 }
@@ -425,7 +386,7 @@ int abg_fm_map_seqs(abg_fm* f, const char* seqs, const uint64_t* offsets, uint64
 		if (f->qdev) { (void)hipStreamSynchronize(f->stream); (void)hipFree(f->qdev); f->qdev = nullptr; f->qcap = 0; }
 		const size_t cap = std::max<size_t>(need, 1u << 20);
 		const hipError_t e = hipMalloc(&f->qdev, cap);
-		if (!fm_ok(f, e, "device memory for the reads")) return fm_code_of(e);
+		if (e != hipSuccess) return st::fail(f->error, e, "device memory for the reads");
 		f->qcap = cap;
 	}
 	// lanes: f->waves waves a CU (abg_fm_tune), fewer where the memo of the call's longest read would pass 1 GiB, and no more than reads
@@ -436,28 +397,28 @@ int abg_fm_map_seqs(abg_fm* f, const char* seqs, const uint64_t* offsets, uint64
 	if (entries > f->memo_cap) {
 		if (f->memo) { (void)hipStreamSynchronize(f->stream); (void)hipFree(f->memo); f->memo = nullptr; f->memo_cap = 0; }
 		hipError_t e = hipMalloc((void**)&f->memo, entries * 8);
-		if (!fm_ok(f, e, "device memory for the memo")) return fm_code_of(e);
+		if (e != hipSuccess) return st::fail(f->error, e, "device memory for the memo");
 		f->memo_cap = entries;
 		e = hipMemsetAsync(f->memo, 0, entries * 8, f->stream); // (the kernel leaves it zero)
-		if (!fm_ok(f, e, "clearing the memo")) return fm_code_of(e);
+		if (e != hipSuccess) return st::fail(f->error, e, "clearing the memo");
 	}
 	char* base = (char*)f->qdev;
 	hipError_t e = hipMemcpyAsync(base, seqs + a, total, hipMemcpyHostToDevice, f->stream);
 	if (e == hipSuccess) e = hipMemcpyAsync(base + off_at, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, f->stream);
 	if (e == hipSuccess) e = hipMemsetAsync(f->ticket, 0, 16, f->stream);
-	if (!fm_ok(f, e, "copying the reads to the device")) return fm_code_of(e);
+	if (e != hipSuccess) return st::fail(f->error, e, "copying the reads to the device");
 	{
-		Timed t(f, "fm_map");
+		st::Timed t(f->prof, f->stream, "fm_map", f->profiling);
 		k_fm_map<<<(unsigned)(lanes / 256), 256, 0, f->stream>>>(f->view, f->sa, (const unsigned char*)base, (const uint64_t*)(base + off_at), n, min_len, flags,
 		    f->memo, (uint32_t)lanes, f->ticket, f->profiling ? f->ticket + 1 : nullptr, (abg::FMHit*)(base + hit_at));
 		e = hipGetLastError();
-		if (!fm_ok(f, e, "the search kernel launch")) return fm_code_of(e);
+		if (e != hipSuccess) return st::fail(f->error, e, "the search kernel launch");
 	}
 	unsigned long long steps = 0;
 	e = hipMemcpyAsync(out, base + hit_at, n * 2 * sizeof(abg::FMHit), hipMemcpyDeviceToHost, f->stream);
 	if (e == hipSuccess && f->profiling) e = hipMemcpyAsync(&steps, f->ticket + 1, 8, hipMemcpyDeviceToHost, f->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(f->stream); // (also keeps `rel` alive until its copy is done)
-	if (!fm_ok(f, e, "reading the matches back")) return fm_code_of(e);
+	if (e != hipSuccess) return st::fail(f->error, e, "reading the matches back");
 	f->steps += steps;
 	return ABG_OK;
 }
@@ -475,7 +436,7 @@ int abg_fm_sync(abg_fm* f)
 	if (!f) return ABG_EINVAL;
 	(void)hipSetDevice(f->device);
 	const hipError_t e = hipStreamSynchronize(f->stream);
-	return fm_ok(f, e, "hipStreamSynchronize") ? ABG_OK : fm_code_of(e);
+	return e == hipSuccess ? ABG_OK : st::fail(f->error, e, "hipStreamSynchronize");
 }
 
 int abg_fm_profile(abg_fm* f, int on)
@@ -488,16 +449,12 @@ int abg_fm_profile_get(abg_fm* f, const char* name, double* total_ms, uint64_t* 
 {
 	if (!f || !name) return ABG_EINVAL;
 	(void)hipSetDevice(f->device);
-	prof_drain(f);
 	if (!strcmp(name, "fm_map_steps")) { // not a kernel: the search steps of the profiled abg_fm_map_seqs calls, as `launches`
 		if (total_ms) *total_ms = 0;
 		if (launches) *launches = f->steps;
 		return ABG_OK;
 	}
-	auto it = f->prof.find(name);
-	if (total_ms) *total_ms = it == f->prof.end() ? 0 : it->second.ms;
-	if (launches) *launches = it == f->prof.end() ? 0 : it->second.launches;
-	return ABG_OK;
+	return f->prof.get(name, total_ms, launches);
 }
 
 } // extern "C"

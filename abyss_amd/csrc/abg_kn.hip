@@ -23,12 +23,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/abyss_amd.h"
 #include "abg_kn.h"
+#include "abg_stage.h"
+
+namespace st = abg::stage;
 
 namespace {
 
@@ -121,8 +123,6 @@ __global__ void __launch_bounds__(256) k_kn_hash(abg::KnParams p, const uint64_t
 	}
 }
 
-struct Prof { double ms = 0; uint64_t launches = 0; };
-
 // A piece of the caller's sequences: `len` characters from seqs + at.  A sequence that does not fit a slot is cut into pieces
 // that overlap by k - 1 characters, so that each of its windows lies in exactly one piece: a piece owns the windows that start
 // at its first `own` positions (all of them for the last piece of a sequence, len - k + 1 for the others, whose last k - 1
@@ -153,14 +153,13 @@ struct abg_kn {
 	unsigned long long* d_count = nullptr;
 	uint32_t cus = 256;
 	bool profiling = false;
-	std::map<std::string, Prof> prof;
-	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
+	st::Profile prof;
 	std::string error;
 	~abg_kn()
 	{
 		(void)hipSetDevice(device);
 		if (stream) (void)hipStreamSynchronize(stream);
-		for (auto& e : pending) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
+		prof.drop();
 		for (int i = 0; i < 2; i++) {
 			if (pin[i]) (void)hipHostFree(pin[i]);
 			if (dev[i]) (void)hipFree(dev[i]);
@@ -178,41 +177,6 @@ struct abg_kn {
 namespace {
 
 std::string g_kn_create_error;
-
-bool kn_ok(abg_kn* f, hipError_t e, const char* what)
-{
-	if (e == hipSuccess) return true;
-	(void)hipGetLastError();
-	f->error = std::string(what) + " failed: " + hipGetErrorString(e);
-	return false;
-}
-int kn_code_of(hipError_t e) { return e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL; }
-
-struct Timed { // brackets one launch with events when profiling
-	abg_kn* f; const char* name; hipEvent_t a = nullptr, b = nullptr;
-	Timed(abg_kn* f, const char* name) : f(f), name(name)
-	{
-		if (!f->profiling) return;
-		(void)hipEventCreate(&a); (void)hipEventCreate(&b);
-		(void)hipEventRecord(a, f->stream);
-	}
-	~Timed()
-	{
-		if (!a) return;
-		(void)hipEventRecord(b, f->stream);
-		f->pending.push_back({ name, { a, b } });
-	}
-};
-void prof_drain(abg_kn* f)
-{
-	for (auto& e : f->pending) {
-		float ms = 0;
-		(void)hipEventSynchronize(e.second.second);
-		if (hipEventElapsedTime(&ms, e.second.first, e.second.second) == hipSuccess) { f->prof[e.first].ms += ms; f->prof[e.first].launches++; }
-		(void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second);
-	}
-	f->pending.clear();
-}
 
 // Staged bytes that fit a slot: each piece and its 'N', then padding up to a multiple of 32 plus KN_PAD (slot is a multiple of 32)
 uint64_t slot_room(const abg_kn* f) { return f->slot - abg::KN_PAD - 32; }
@@ -262,11 +226,11 @@ unsigned grid_for(abg_kn* f, uint64_t n) { return (unsigned)std::max<uint64_t>(1
 // codes and mask of a staged slot of `len` characters (+ padding)
 int launch_pack(abg_kn* f, const char* dev, uint64_t len)
 {
-	Timed t(f, "kn_pack");
+	st::Timed t(f->prof, f->stream, "kn_pack", f->profiling);
 	const uint64_t nwords = (len + 31) / 32 + abg::KN_PAD / 32;
 	k_kn_pack<<<grid_for(f, nwords), 256, 0, f->stream>>>((const uint4*)dev, nwords, f->codes, f->bad);
 	const hipError_t e = hipGetLastError();
-	return kn_ok(f, e, "the pack kernel launch") ? ABG_OK : kn_code_of(e);
+	return e == hipSuccess ? ABG_OK : st::fail(f->error, e, "the pack kernel launch");
 }
 
 #define KN_DISPATCH(NWV, CALL) \
@@ -275,12 +239,12 @@ int launch_pack(abg_kn* f, const char* dev, uint64_t len)
 
 int launch_insert(abg_kn* f, uint64_t npos)
 {
-	Timed t(f, "kn_insert");
+	st::Timed t(f->prof, f->stream, "kn_insert", f->profiling);
 #define KN_INSERT(N) k_kn_insert<N><<<grid_for(f, npos), 256, 0, f->stream>>>(f->p, f->codes, f->bad, npos, f->levels)
 	KN_DISPATCH(f->p.nw, KN_INSERT)
 #undef KN_INSERT
 	const hipError_t e = hipGetLastError();
-	return kn_ok(f, e, "the insert kernel launch") ? ABG_OK : kn_code_of(e);
+	return e == hipSuccess ? ABG_OK : st::fail(f->error, e, "the insert kernel launch");
 }
 
 bool grow_aux(abg_kn* f, size_t bytes)
@@ -288,7 +252,8 @@ bool grow_aux(abg_kn* f, size_t bytes)
 	if (bytes <= f->aux_cap) return true;
 	if (f->aux) { (void)hipStreamSynchronize(f->stream); (void)hipFree(f->aux); f->aux = nullptr; f->aux_cap = 0; }
 	const size_t cap = std::max<size_t>(bytes, 1u << 20);
-	if (!kn_ok(f, hipMalloc((void**)&f->aux, cap), "device memory for the results")) return false;
+	const hipError_t e = hipMalloc((void**)&f->aux, cap);
+	if (e != hipSuccess) { (void)st::fail(f->error, e, "device memory for the results"); return false; }
 	f->aux_cap = cap;
 	return true;
 }
@@ -298,7 +263,7 @@ int wait_slot(abg_kn* f, int s)
 {
 	if (!f->busy[s]) return ABG_OK;
 	const hipError_t e = hipEventSynchronize(f->done[s]);
-	if (!kn_ok(f, e, "waiting for a staging slot")) return kn_code_of(e);
+	if (e != hipSuccess) return st::fail(f->error, e, "waiting for a staging slot");
 	f->busy[s] = false;
 	return ABG_OK;
 }
@@ -311,7 +276,7 @@ int upload(abg_kn* f, int s, const char* seqs, const uint64_t* off, uint64_t n, 
 	*len = stage(f, f->pin[s], seqs, off, n, i, c);
 	const uint64_t padded = (*len + 31) / 32 * 32 + abg::KN_PAD;
 	hipError_t e = hipMemcpyAsync(f->dev[s], f->pin[s], padded, hipMemcpyHostToDevice, f->stream);
-	if (!kn_ok(f, e, "copying reads to the device")) return kn_code_of(e);
+	if (e != hipSuccess) return st::fail(f->error, e, "copying reads to the device");
 	return launch_pack(f, f->dev[s], *len);
 }
 
@@ -327,22 +292,21 @@ int abg_kn_create(int device, uint64_t full_bits, uint32_t levels, uint32_t k, u
 		g_kn_create_error = "bad filter size, level count, k (1..192) or window";
 		return ABG_EINVAL;
 	}
-	int n = 0;
-	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); g_kn_create_error = "no HIP device available (abyss_amd has no CPU fallback)"; return ABG_ENODEV; }
-	if (device < 0 || device >= n) { g_kn_create_error = "HIP device ordinal out of range"; return ABG_ENODEV; }
+	hipStream_t stream = nullptr;
+	const int opened = st::open_device(device, "Konnector filter", g_kn_create_error, &stream, 1);
+	if (opened != ABG_OK) return opened;
 	abg_kn* f = new abg_kn;
 	f->device = device;
+	f->stream = stream;
 	f->p = abg::make_kn_params(k, seed, full_bits, levels, start, end);
 	f->level_bits = end - start + 1;
 	f->level_bytes = (f->level_bits + 7) / 8;
 	if (const char* v = getenv("ABG_KN_SLOT_BYTES")) f->slot = std::max<size_t>(1024, strtoull(v, nullptr, 10)) / 32 * 32; // (tests)
-	hipError_t e = hipSetDevice(device);
 	hipDeviceProp_t prop;
-	if (e == hipSuccess && hipGetDeviceProperties(&prop, device) == hipSuccess) f->cus = (uint32_t)prop.multiProcessorCount;
+	if (hipGetDeviceProperties(&prop, device) == hipSuccess) f->cus = (uint32_t)prop.multiProcessorCount;
 	const size_t lbytes = (size_t)f->p.level_words * 4 * levels;
 	const size_t words = f->slot / 32 + 16;
-	if (e == hipSuccess) e = hipStreamCreate(&f->stream);
-	if (e == hipSuccess) e = hipMalloc((void**)&f->levels, lbytes);
+	hipError_t e = hipMalloc((void**)&f->levels, lbytes);
 	if (e == hipSuccess) e = hipMemsetAsync(f->levels, 0, lbytes, f->stream);
 	if (e == hipSuccess) e = hipMalloc((void**)&f->codes, words * 8);
 	if (e == hipSuccess) e = hipMalloc((void**)&f->bad, words * 4);
@@ -354,9 +318,7 @@ int abg_kn_create(int device, uint64_t full_bits, uint32_t levels, uint32_t k, u
 	}
 	if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
 	if (e != hipSuccess) {
-		(void)hipGetLastError();
-		g_kn_create_error = std::string("creating the Konnector filter failed: ") + hipGetErrorString(e);
-		const int rc = kn_code_of(e);
+		const int rc = st::create_fail(g_kn_create_error, e, "Konnector filter");
 		delete f;
 		return rc;
 	}
@@ -373,7 +335,7 @@ int abg_kn_import(abg_kn* f, uint32_t level, const uint8_t* bytes)
 	(void)hipSetDevice(f->device);
 	hipError_t e = hipMemcpyAsync(f->levels + (size_t)level * f->p.level_words, bytes, f->level_bytes, hipMemcpyHostToDevice, f->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
-	return kn_ok(f, e, "copying a level to the device") ? ABG_OK : kn_code_of(e);
+	return e == hipSuccess ? ABG_OK : st::fail(f->error, e, "copying a level to the device");
 }
 
 int abg_kn_export(abg_kn* f, uint32_t level, uint8_t* bytes)
@@ -382,7 +344,7 @@ int abg_kn_export(abg_kn* f, uint32_t level, uint8_t* bytes)
 	(void)hipSetDevice(f->device);
 	hipError_t e = hipMemcpyAsync(bytes, f->levels + (size_t)level * f->p.level_words, f->level_bytes, hipMemcpyDeviceToHost, f->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
-	return kn_ok(f, e, "copying a level to the host") ? ABG_OK : kn_code_of(e);
+	return e == hipSuccess ? ABG_OK : st::fail(f->error, e, "copying a level to the host");
 }
 
 int abg_kn_insert_seqs(abg_kn* f, const char* seqs, const uint64_t* offsets, uint64_t n)
@@ -399,7 +361,7 @@ int abg_kn_insert_seqs(abg_kn* f, const char* seqs, const uint64_t* offsets, uin
 		if (rc == ABG_OK) rc = launch_insert(f, len);
 		if (rc == ABG_OK) {
 			const hipError_t e = hipEventRecord(f->done[s], f->stream);
-			if (!kn_ok(f, e, "hipEventRecord")) rc = kn_code_of(e);
+			if (e != hipSuccess) rc = st::fail(f->error, e, "hipEventRecord");
 			else f->busy[s] = true;
 		}
 	}
@@ -421,18 +383,18 @@ int abg_kn_contains_seqs(abg_kn* f, const char* seqs, const uint64_t* offsets, u
 		rc = upload(f, s, seqs, offsets, n, i, c, &len);
 		if (rc != ABG_OK) break;
 		{
-			Timed t(f, "kn_contains");
+			st::Timed t(f->prof, f->stream, "kn_contains", f->profiling);
 			const unsigned grid = grid_for(f, len);
 #define KN_CONTAINS(N) k_kn_contains<N><<<grid, 256, 0, f->stream>>>(f->p, f->codes, f->bad, len, f->levels, inverse, f->aux)
 			KN_DISPATCH(f->p.nw, KN_CONTAINS)
 #undef KN_CONTAINS
 			const hipError_t e = hipGetLastError();
-			if (!kn_ok(f, e, "the probe kernel launch")) { rc = kn_code_of(e); break; }
+			if (e != hipSuccess) { rc = st::fail(f->error, e, "the probe kernel launch"); break; }
 		}
 		bits.resize((len + 63) / 64);
 		hipError_t e = hipMemcpyAsync(bits.data(), f->aux, bits.size() * 8, hipMemcpyDeviceToHost, f->stream);
 		if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
-		if (!kn_ok(f, e, "reading the probes back")) { rc = kn_code_of(e); break; }
+		if (e != hipSuccess) { rc = st::fail(f->error, e, "reading the probes back"); break; }
 		// staged position -> the caller's position: each piece's flags go to where it came from, up to the positions it owns
 		// (the next piece writes the rest)
 		uint64_t at = 0;
@@ -452,7 +414,7 @@ int abg_kn_popcount(abg_kn* f, uint64_t* per_level)
 	for (uint32_t l = 0; l < f->p.levels; l++) {
 		hipError_t e = hipMemsetAsync(f->d_count, 0, 8, f->stream);
 		if (e == hipSuccess) {
-			Timed t(f, "kn_popcount");
+			st::Timed t(f->prof, f->stream, "kn_popcount", f->profiling);
 			const uint64_t n16 = f->p.level_words / 4;
 			k_kn_popcount<<<grid_for(f, n16), 256, 0, f->stream>>>((const uint4*)(f->levels + (size_t)l * f->p.level_words), n16, f->d_count);
 			e = hipGetLastError();
@@ -460,7 +422,7 @@ int abg_kn_popcount(abg_kn* f, uint64_t* per_level)
 		unsigned long long c = 0;
 		if (e == hipSuccess) e = hipMemcpyAsync(&c, f->d_count, 8, hipMemcpyDeviceToHost, f->stream);
 		if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
-		if (!kn_ok(f, e, "counting a level's bits")) return kn_code_of(e);
+		if (e != hipSuccess) return st::fail(f->error, e, "counting a level's bits");
 		per_level[l] = c;
 	}
 	return ABG_OK;
@@ -484,18 +446,18 @@ int abg_kn_hash_seq(abg_kn* f, const char* seq, uint64_t len, uint64_t* hash, ui
 	unsigned long long* di = f->aux + npos;
 	unsigned char* dv = (unsigned char*)(f->aux + 2 * npos);
 	{
-		Timed t(f, "kn_hash");
+		st::Timed t(f->prof, f->stream, "kn_hash", f->profiling);
 #define KN_HASH(N) k_kn_hash<N><<<grid_for(f, npos), 256, 0, f->stream>>>(f->p, f->codes, f->bad, npos, dh, di, dv)
 		KN_DISPATCH(f->p.nw, KN_HASH)
 #undef KN_HASH
 		const hipError_t e = hipGetLastError();
-		if (!kn_ok(f, e, "the hash kernel launch")) return kn_code_of(e);
+		if (e != hipSuccess) return st::fail(f->error, e, "the hash kernel launch");
 	}
 	hipError_t e = hipMemcpyAsync(hash, dh, npos * 8, hipMemcpyDeviceToHost, f->stream);
 	if (e == hipSuccess) e = hipMemcpyAsync(index, di, npos * 8, hipMemcpyDeviceToHost, f->stream);
 	if (e == hipSuccess) e = hipMemcpyAsync(valid, dv, npos, hipMemcpyDeviceToHost, f->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
-	return kn_ok(f, e, "reading the hashes back") ? ABG_OK : kn_code_of(e);
+	return e == hipSuccess ? ABG_OK : st::fail(f->error, e, "reading the hashes back");
 }
 
 int abg_kn_sync(abg_kn* f)
@@ -504,7 +466,7 @@ int abg_kn_sync(abg_kn* f)
 	(void)hipSetDevice(f->device);
 	const hipError_t e = hipStreamSynchronize(f->stream);
 	f->busy[0] = f->busy[1] = false;
-	return kn_ok(f, e, "hipStreamSynchronize") ? ABG_OK : kn_code_of(e);
+	return e == hipSuccess ? ABG_OK : st::fail(f->error, e, "hipStreamSynchronize");
 }
 
 int abg_kn_profile(abg_kn* f, int on)
@@ -517,11 +479,7 @@ int abg_kn_profile_get(abg_kn* f, const char* name, double* total_ms, uint64_t* 
 {
 	if (!f || !name) return ABG_EINVAL;
 	(void)hipSetDevice(f->device);
-	prof_drain(f);
-	auto it = f->prof.find(name);
-	if (total_ms) *total_ms = it == f->prof.end() ? 0 : it->second.ms;
-	if (launches) *launches = it == f->prof.end() ? 0 : it->second.launches;
-	return ABG_OK;
+	return f->prof.get(name, total_ms, launches);
 }
 
 } // extern "C"

@@ -19,12 +19,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/abyss_amd.h"
 #include "abg_mc.h"
+#include "abg_stage.h"
+
+namespace st = abg::stage;
 
 namespace {
 
@@ -160,8 +162,6 @@ __global__ __launch_bounds__(abg::MC_BLOCK) void mc_splice_kernel(const uint64_t
 	if (mine) atomicAdd(&acgt[mine_path], mine);
 }
 
-struct Prof { double ms = 0; uint64_t launches = 0; };
-
 } // namespace
 
 struct abg_mc {
@@ -181,8 +181,7 @@ struct abg_mc {
 	std::vector<uint8_t> seqs;
 	std::string logs;
 	int profiling = 0;
-	std::map<std::string, Prof> prof;
-	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
+	st::Profile prof;
 	uint64_t redone = 0, bytes = 0;
 	std::string error;
 	void free_contigs()
@@ -197,7 +196,7 @@ struct abg_mc {
 	{
 		(void)hipSetDevice(device);
 		if (stream) (void)hipStreamSynchronize(stream);
-		for (auto& e : pending) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
+		prof.drop();
 		free_contigs();
 		if (din) (void)hipFree(din);
 		if (dside) (void)hipFree(dside);
@@ -210,51 +209,6 @@ namespace {
 
 std::string g_mc_create_error;
 
-int mc_fail(abg_mc* s, hipError_t e, const char* what)
-{
-	(void)hipGetLastError();
-	s->error = std::string(what) + " failed: " + hipGetErrorString(e);
-	return e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL;
-}
-
-void prof_drain(abg_mc* s)
-{
-	for (auto& e : s->pending) {
-		float ms = 0;
-		(void)hipEventSynchronize(e.second.second);
-		if (hipEventElapsedTime(&ms, e.second.first, e.second.second) == hipSuccess) { s->prof[e.first].ms += ms; s->prof[e.first].launches++; }
-		(void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second);
-	}
-	s->pending.clear();
-}
-
-hipError_t grow(void** dev, size_t* cap, size_t need)
-{
-	if (need <= *cap) return hipSuccess;
-	if (*dev) (void)hipFree(*dev);
-	*dev = nullptr;
-	*cap = 0;
-	const hipError_t e = hipMalloc(dev, need);
-	if (e == hipSuccess) *cap = need;
-	return e;
-}
-
-unsigned long long env_u64(const char* name, unsigned long long lo, unsigned long long hi, unsigned long long dflt)
-{
-	const char* v = getenv(name);
-	if (!v || !*v) return dflt;
-	const unsigned long long t = strtoull(v, nullptr, 10);
-	return std::max(lo, std::min(hi, t));
-}
-
-size_t up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-struct Timed {
-	abg_mc* s; const char* name; hipEvent_t t0 = nullptr, t1 = nullptr;
-	Timed(abg_mc* s, const char* name) : s(s), name(name) { if (s->profiling) { (void)hipEventCreate(&t0); (void)hipEventCreate(&t1); (void)hipEventRecord(t0, s->stream); } }
-	~Timed() { if (s->profiling) { (void)hipEventRecord(t1, s->stream); s->pending.push_back({ name, { t0, t1 } }); } }
-};
-
 } // namespace
 
 extern "C" {
@@ -263,22 +217,14 @@ int abg_mc_create(int device, abg_mc** out)
 {
 	if (!out) return ABG_EINVAL;
 	*out = nullptr;
-	int n = 0;
-	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); g_mc_create_error = "no HIP device available (abyss_amd has no CPU fallback)"; return ABG_ENODEV; }
-	if (device < 0 || device >= n) { g_mc_create_error = "HIP device ordinal out of range"; return ABG_ENODEV; }
+	hipStream_t stream = nullptr;
+	const int rc = st::open_device(device, "path merger", g_mc_create_error, &stream, 1);
+	if (rc != ABG_OK) return rc;
 	abg_mc* s = new abg_mc;
 	s->device = device;
-	hipError_t e = hipSetDevice(device);
-	if (e == hipSuccess) e = hipStreamCreate(&s->stream);
-	if (e != hipSuccess) {
-		(void)hipGetLastError();
-		g_mc_create_error = std::string("creating the path merger failed: ") + hipGetErrorString(e);
-		const int rc = e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL;
-		delete s;
-		return rc;
-	}
-	s->tile = env_u64("ABG_MC_TILE", 16, 1ull << 24, s->tile) / 16 * 16;
-	s->batch = env_u64("ABG_MC_BATCH", 1, 1ull << 24, s->batch);
+	s->stream = stream;
+	s->tile = st::env_u64("ABG_MC_TILE", 16, 1ull << 24, s->tile) / 16 * 16;
+	s->batch = st::env_u64("ABG_MC_BATCH", 1, 1ull << 24, s->batch);
 	*out = s;
 	return ABG_OK;
 }
@@ -309,7 +255,7 @@ int abg_mc_set_contigs(abg_mc* s, const uint8_t* bytes, const uint64_t* offsets,
 	(void)hipSetDevice(s->device);
 	(void)hipStreamSynchronize(s->stream);
 	s->free_contigs();
-	s->store.assign(up(total + 2 * abg::MC_PAD, 8), 0);
+	s->store.assign(st::up(total + 2 * abg::MC_PAD, 8), 0);
 	if (total) memcpy(s->store.data() + abg::MC_PAD, bytes, total);
 	s->off.assign(offsets, offsets + n + 1);
 	s->reversible.assign(n, 1);
@@ -323,7 +269,7 @@ int abg_mc_set_contigs(abg_mc* s, const uint8_t* bytes, const uint64_t* offsets,
 	if (e == hipSuccess) e = hipMemcpyAsync(s->d_store, s->store.data(), s->store.size(), hipMemcpyHostToDevice, s->stream);
 	if (e == hipSuccess) e = hipMemcpyAsync(s->d_off, s->off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-	if (e != hipSuccess) { s->free_contigs(); return mc_fail(s, e, "uploading the contigs"); }
+	if (e != hipSuccess) { s->free_contigs(); return st::fail(s->error, e, "uploading the contigs"); }
 	s->have_contigs = true;
 	return ABG_OK;
 }
@@ -397,13 +343,13 @@ int abg_mc_merge(abg_mc* s, uint32_t k, uint64_t npaths, const uint64_t* node_of
 		const size_t base = s->seqs.size();
 		if (total > 0) {
 			// the input block: paths, segments, nodes, overlaps; the output block: flags, counts, bytes
-			const size_t paths_at = 0, segs_at = up(nb * sizeof(MCPath), 64), nodes_at = segs_at + up(segs.size() * sizeof(abg::MCSeg), 64),
-			             ov_at = nodes_at + up(nn * 4, 64), in_bytes = ov_at + up(nn * 4, 64);
-			const size_t flags_at = 0, counts_at = up(nb * 4, 64), out_at = counts_at + up(nb * 8, 64), out_bytes = out_at + up(total, 16);
-			hipError_t e = grow(&s->din, &s->in_cap, in_bytes);
-			if (e == hipSuccess) e = grow(&s->dside, &s->side_cap, up(side, 8) + 64);
-			if (e == hipSuccess) e = grow(&s->dout, &s->out_cap, out_bytes);
-			if (e != hipSuccess) return mc_fail(s, e, "allocating a batch");
+			const size_t paths_at = 0, segs_at = st::up(nb * sizeof(MCPath), 64), nodes_at = segs_at + st::up(segs.size() * sizeof(abg::MCSeg), 64),
+			             ov_at = nodes_at + st::up(nn * 4, 64), in_bytes = ov_at + st::up(nn * 4, 64);
+			const size_t flags_at = 0, counts_at = st::up(nb * 4, 64), out_at = counts_at + st::up(nb * 8, 64), out_bytes = out_at + st::up(total, 16);
+			hipError_t e = st::grow(&s->din, &s->in_cap, in_bytes);
+			if (e == hipSuccess) e = st::grow(&s->dside, &s->side_cap, st::up(side, 8) + 64);
+			if (e == hipSuccess) e = st::grow(&s->dout, &s->out_cap, out_bytes);
+			if (e != hipSuccess) return st::fail(s->error, e, "allocating a batch");
 			char* in = (char*)s->din;
 			char* out = (char*)s->dout;
 			e = hipMemcpyAsync(in + paths_at, paths.data(), nb * sizeof(MCPath), hipMemcpyHostToDevice, s->stream);
@@ -411,28 +357,28 @@ int abg_mc_merge(abg_mc* s, uint32_t k, uint64_t npaths, const uint64_t* node_of
 			if (e == hipSuccess && nn) e = hipMemcpyAsync(in + nodes_at, nodes + n0, nn * 4, hipMemcpyHostToDevice, s->stream);
 			if (e == hipSuccess && nn) e = hipMemcpyAsync(in + ov_at, overlaps + n0, nn * 4, hipMemcpyHostToDevice, s->stream);
 			if (e == hipSuccess) e = hipMemsetAsync(out, 0, out_at, s->stream);
-			if (e != hipSuccess) return mc_fail(s, e, "copying a batch to the device");
+			if (e != hipSuccess) return st::fail(s->error, e, "copying a batch to the device");
 			if (side > 0) {
-				Timed t(s, "mc_junction");
+				st::Timed t(s->prof, s->stream, "mc_junction", s->profiling != 0);
 				hipLaunchKernelGGL(mc_junction_kernel, dim3((unsigned)nb), dim3(64), 0, s->stream, ds, k, (const MCPath*)(in + paths_at), (const int32_t*)(in + nodes_at),
 				    (const uint32_t*)(in + ov_at), (uint8_t*)s->dside, (uint32_t*)(out + flags_at));
 				e = hipGetLastError();
 			}
-			if (e != hipSuccess) return mc_fail(s, e, "launching the junction pass");
+			if (e != hipSuccess) return st::fail(s->error, e, "launching the junction pass");
 			{
-				Timed t(s, "mc_splice");
+				st::Timed t(s->prof, s->stream, "mc_splice", s->profiling != 0);
 				const uint64_t tiles = (total + s->tile - 1) / s->tile;
 				hipLaunchKernelGGL(mc_splice_kernel, dim3((unsigned)tiles), dim3(abg::MC_BLOCK), 0, s->stream, (const uint64_t*)s->d_store, (const uint64_t*)s->dside,
 				    (const abg::MCSeg*)(in + segs_at), (uint64_t)segs.size(), total, s->tile, (uint8_t*)(out + out_at), (unsigned long long*)(out + counts_at));
 				e = hipGetLastError();
 			}
-			if (e != hipSuccess) return mc_fail(s, e, "launching the splice pass");
+			if (e != hipSuccess) return st::fail(s->error, e, "launching the splice pass");
 			s->seqs.resize(base + total);
 			e = hipMemcpyAsync(flags.data(), out + flags_at, nb * 4, hipMemcpyDeviceToHost, s->stream);
 			if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), out + counts_at, nb * 8, hipMemcpyDeviceToHost, s->stream);
 			if (e == hipSuccess) e = hipMemcpyAsync(s->seqs.data() + base, out + out_at, total, hipMemcpyDeviceToHost, s->stream);
 			if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-			if (e != hipSuccess) return mc_fail(s, e, "the merge");
+			if (e != hipSuccess) return st::fail(s->error, e, "the merge");
 			s->bytes += total;
 		}
 		// the flagged paths again, on the host; when there is one, the batch's bytes are put together path by path
@@ -478,15 +424,11 @@ int abg_mc_profile_get(abg_mc* s, const char* name, double* total_ms, uint64_t* 
 {
 	if (!s || !name) return ABG_EINVAL;
 	(void)hipSetDevice(s->device);
-	prof_drain(s);
 	if (total_ms) *total_ms = 0;
 	// not kernels: the paths merged again on the host, and the bytes the splice pass wrote
 	if (!strcmp(name, "mc_redone")) { if (launches) *launches = s->redone; return ABG_OK; }
 	if (!strcmp(name, "mc_bytes")) { if (launches) *launches = s->bytes; return ABG_OK; }
-	auto it = s->prof.find(name);
-	if (total_ms) *total_ms = it == s->prof.end() ? 0 : it->second.ms;
-	if (launches) *launches = it == s->prof.end() ? 0 : it->second.launches;
-	return ABG_OK;
+	return s->prof.get(name, total_ms, launches);
 }
 
 } // extern "C"

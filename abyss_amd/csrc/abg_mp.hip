@@ -26,12 +26,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/abyss_amd.h"
 #include "abg_mp.h"
+#include "abg_stage.h"
+
+namespace st = abg::stage;
 
 static_assert(sizeof(abg_mp_record) == sizeof(abg::MPRecord), "abg_mp_record is MPRecord");
 
@@ -134,8 +136,6 @@ __global__ __launch_bounds__(64) void mp_wave_kernel(const MPPair* __restrict__ 
 	if (lane == 0) records[blockIdx.x] = r;
 }
 
-struct Prof { double ms = 0; uint64_t launches = 0; };
-
 struct Slot { // a stream and what a batch in flight on it owns
 	hipStream_t stream = nullptr;
 	void* d_in = nullptr; size_t in_cap = 0;
@@ -159,8 +159,7 @@ struct abg_mp {
 	void* d_tables = nullptr; // the match table, the complement table, min_identity
 	float table_identity = 0;
 	bool tables_ready = false;
-	std::map<std::string, Prof> prof;
-	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
+	st::Profile prof;
 	uint64_t spilled = 0, host_run = 0, cells = 0, launches = 0, relaunched = 0;
 	std::string error;
 	~abg_mp()
@@ -168,7 +167,7 @@ struct abg_mp {
 		(void)hipSetDevice(device);
 		for (Slot& s : slot)
 			if (s.stream) (void)hipStreamSynchronize(s.stream);
-		for (auto& e : pending) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
+		prof.drop();
 		for (Slot& s : slot) {
 			for (void* p : { s.d_in, s.d_meta, s.d_spill })
 				if (p) (void)hipFree(p);
@@ -185,61 +184,22 @@ std::string g_mp_create_error;
 constexpr size_t TABLE_AT = 0, COMP_AT = 256 * 8 * 4, IDENTITY_AT = COMP_AT + 256, IDENTITY_N = 2 * KMAX + 1, TABLES_BYTES = IDENTITY_AT + IDENTITY_N * 4;
 constexpr uint64_t MP_MAX_SPILL = 1ull << 35, MP_MAX_BATCH = 1ull << 24;
 
-int mp_fail(abg_mp* s, hipError_t e, const char* what)
-{
-	(void)hipGetLastError();
-	s->error = std::string(what) + " failed: " + hipGetErrorString(e);
-	return e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL;
-}
-
-void prof_drain(abg_mp* s)
-{
-	for (auto& e : s->pending) {
-		float ms = 0;
-		(void)hipEventSynchronize(e.second.second);
-		if (hipEventElapsedTime(&ms, e.second.first, e.second.second) == hipSuccess) { s->prof[e.first].ms += ms; s->prof[e.first].launches++; }
-		(void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second);
-	}
-	s->pending.clear();
-}
-
-hipError_t grow(void** dev, size_t* cap, size_t need)
-{
-	if (need <= *cap) return hipSuccess;
-	if (*dev) (void)hipFree(*dev);
-	*dev = nullptr;
-	*cap = 0;
-	const hipError_t e = hipMalloc(dev, need);
-	if (e == hipSuccess) *cap = need;
-	return e;
-}
-
-unsigned long long env_u64(const char* name, unsigned long long lo, unsigned long long hi, unsigned long long dflt)
-{
-	const char* v = getenv(name);
-	if (!v || !*v) return dflt;
-	const unsigned long long t = strtoull(v, nullptr, 10);
-	return std::max(lo, std::min(hi, t));
-}
-
-size_t up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // the three tables of a call: the first two once, min_identity whenever the identity changes
 int mp_tables(abg_mp* s, float identity)
 {
 	hipError_t e = hipSuccess;
 	if (!s->d_tables) e = hipMalloc(&s->d_tables, TABLES_BYTES);
-	if (e != hipSuccess) return mp_fail(s, e, "allocating the tables");
+	if (e != hipSuccess) return st::fail(s->error, e, "allocating the tables");
 	if (s->tables_ready && memcmp(&identity, &s->table_identity, sizeof identity) == 0) return ABG_OK;
 	for (Slot& q : s->slot) // (a kernel of the call before may still read them)
-		if ((e = hipStreamSynchronize(q.stream)) != hipSuccess) return mp_fail(s, e, "waiting for a stream");
+		if ((e = hipStreamSynchronize(q.stream)) != hipSuccess) return st::fail(s->error, e, "waiting for a stream");
 	std::vector<uint8_t> host(TABLES_BYTES);
 	const std::vector<uint32_t> table = abg::mp_match_table(), ident = abg::mp_identity_table(identity, (uint32_t)IDENTITY_N - 1);
 	memcpy(host.data() + TABLE_AT, table.data(), 256 * 8 * 4);
 	for (int c = 0; c < 256; ++c) host[COMP_AT + c] = abg::ov_complement((uint8_t)c);
 	memcpy(host.data() + IDENTITY_AT, ident.data(), IDENTITY_N * 4);
 	e = hipMemcpy(s->d_tables, host.data(), TABLES_BYTES, hipMemcpyHostToDevice);
-	if (e != hipSuccess) return mp_fail(s, e, "uploading the tables");
+	if (e != hipSuccess) return st::fail(s->error, e, "uploading the tables");
 	s->tables_ready = true;
 	s->table_identity = identity;
 	return ABG_OK;
@@ -275,32 +235,30 @@ int mp_launch(abg_mp* s, Slot& q, Call& c, const uint64_t* ids, uint64_t n)
 		s->cells += la * lb;
 	}
 	const unsigned long long spill_cells = s->spill_bytes / sizeof(MPCell);
-	q.rec_at = up(n * sizeof(MPPair), 64);
-	q.used_at = q.rec_at + up(n * sizeof(MPRecord), 64);
-	hipError_t e = grow(&q.d_in, &q.in_cap, std::max<size_t>(q.in.size(), 64));
-	if (e == hipSuccess) e = grow(&q.d_meta, &q.meta_cap, q.used_at + 64);
-	if (e == hipSuccess) e = grow(&q.d_spill, &q.spill_cap, std::max<size_t>(spill_cells * sizeof(MPCell), 64));
-	if (e != hipSuccess) return mp_fail(s, e, "allocating a launch");
+	q.rec_at = st::up(n * sizeof(MPPair), 64);
+	q.used_at = q.rec_at + st::up(n * sizeof(MPRecord), 64);
+	hipError_t e = st::grow(&q.d_in, &q.in_cap, std::max<size_t>(q.in.size(), 64));
+	if (e == hipSuccess) e = st::grow(&q.d_meta, &q.meta_cap, q.used_at + 64);
+	if (e == hipSuccess) e = st::grow(&q.d_spill, &q.spill_cap, std::max<size_t>(spill_cells * sizeof(MPCell), 64));
+	if (e != hipSuccess) return st::fail(s->error, e, "allocating a launch");
 	char* meta = (char*)q.d_meta;
 	if (!q.in.empty()) e = hipMemcpyAsync(q.d_in, q.in.data(), q.in.size(), hipMemcpyHostToDevice, q.stream);
 	if (e == hipSuccess) e = hipMemcpyAsync(meta, q.pairs.data(), n * sizeof(MPPair), hipMemcpyHostToDevice, q.stream);
 	if (e == hipSuccess) e = hipMemsetAsync(meta + q.used_at, 0, 8, q.stream);
-	if (e != hipSuccess) return mp_fail(s, e, "copying a launch to the device");
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	(void)hipEventCreate(&t0); (void)hipEventCreate(&t1);
-	(void)hipEventRecord(t0, q.stream);
+	if (e != hipSuccess) return st::fail(s->error, e, "copying a launch to the device");
 	const char* tables = (const char*)s->d_tables;
-	hipLaunchKernelGGL(mp_wave_kernel, dim3((unsigned)n), dim3(64), 0, q.stream, (const MPPair*)meta, (const uint8_t*)q.d_in, (const uint32_t*)(tables + TABLE_AT),
-	    (const uint8_t*)(tables + COMP_AT), (const uint32_t*)(tables + IDENTITY_AT), c.min_matches, (MPRecord*)(meta + q.rec_at), (MPCell*)q.d_spill, spill_cells,
-	    (unsigned long long*)(meta + q.used_at));
-	e = hipGetLastError();
-	(void)hipEventRecord(t1, q.stream);
-	s->pending.push_back({ "mp_wave", { t0, t1 } });
-	if (e != hipSuccess) return mp_fail(s, e, "launching the alignment");
+	{
+		st::Timed t(s->prof, q.stream, "mp_wave");
+		hipLaunchKernelGGL(mp_wave_kernel, dim3((unsigned)n), dim3(64), 0, q.stream, (const MPPair*)meta, (const uint8_t*)q.d_in, (const uint32_t*)(tables + TABLE_AT),
+		    (const uint8_t*)(tables + COMP_AT), (const uint32_t*)(tables + IDENTITY_AT), c.min_matches, (MPRecord*)(meta + q.rec_at), (MPCell*)q.d_spill, spill_cells,
+		    (unsigned long long*)(meta + q.used_at));
+		e = hipGetLastError();
+	}
+	if (e != hipSuccess) return st::fail(s->error, e, "launching the alignment");
 	q.recs.resize(n);
 	e = hipMemcpyAsync(q.recs.data(), meta + q.rec_at, n * sizeof(MPRecord), hipMemcpyDeviceToHost, q.stream);
 	if (e == hipSuccess) e = hipMemcpyAsync(&q.used, meta + q.used_at, 8, hipMemcpyDeviceToHost, q.stream);
-	if (e != hipSuccess) return mp_fail(s, e, "queueing the download");
+	if (e != hipSuccess) return st::fail(s->error, e, "queueing the download");
 	q.busy = true;
 	s->launches++;
 	return ABG_OK;
@@ -312,12 +270,12 @@ int mp_collect(abg_mp* s, Slot& q, Call& c)
 	if (!q.busy) return ABG_OK;
 	q.busy = false;
 	hipError_t e = hipStreamSynchronize(q.stream);
-	if (e != hipSuccess) return mp_fail(s, e, "the alignment");
+	if (e != hipSuccess) return st::fail(s->error, e, "the alignment");
 	const unsigned long long spill_cells = s->spill_bytes / sizeof(MPCell), filled = std::min(q.used, spill_cells);
 	std::vector<MPCell> rows((size_t)filled);
 	if (filled) {
 		e = hipMemcpy(rows.data(), q.d_spill, (size_t)filled * sizeof(MPCell), hipMemcpyDeviceToHost);
-		if (e != hipSuccess) return mp_fail(s, e, "fetching the spilled rows");
+		if (e != hipSuccess) return st::fail(s->error, e, "fetching the spilled rows");
 	}
 	for (size_t k = 0; k < q.recs.size(); ++k) {
 		const uint64_t id = q.ids[k];
@@ -337,7 +295,7 @@ int mp_collect(abg_mp* s, Slot& q, Call& c)
 		r.spill = 0;
 		c.out[id] = r;
 	}
-	if (s->pending.size() >= 64) prof_drain(s);
+	s->prof.drain_if(64);
 	return ABG_OK;
 }
 
@@ -374,24 +332,15 @@ int abg_mp_create(int device, abg_mp** out)
 {
 	if (!out) return ABG_EINVAL;
 	*out = nullptr;
-	int n = 0;
-	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); g_mp_create_error = "no HIP device available (abyss_amd has no CPU fallback)"; return ABG_ENODEV; }
-	if (device < 0 || device >= n) { g_mp_create_error = "HIP device ordinal out of range"; return ABG_ENODEV; }
+	hipStream_t stream[2] = { nullptr, nullptr };
+	const int rc = st::open_device(device, "pair aligner", g_mp_create_error, stream, 2);
+	if (rc != ABG_OK) return rc;
 	abg_mp* s = new abg_mp;
 	s->device = device;
-	hipError_t e = hipSetDevice(device);
-	for (Slot& q : s->slot)
-		if (e == hipSuccess) e = hipStreamCreate(&q.stream);
-	if (e != hipSuccess) {
-		(void)hipGetLastError();
-		g_mp_create_error = std::string("creating the pair aligner failed: ") + hipGetErrorString(e);
-		const int rc = e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL;
-		delete s;
-		return rc;
-	}
-	s->max_len = env_u64("ABG_MP_MAX_LEN", 1, abg::MP_KERNEL_MAX, s->max_len);
-	s->spill_bytes = env_u64("ABG_MP_SPILL_BYTES", sizeof(MPCell), MP_MAX_SPILL, s->spill_bytes);
-	s->batch = env_u64("ABG_MP_BATCH", 1, MP_MAX_BATCH, s->batch);
+	for (int i = 0; i < 2; ++i) s->slot[i].stream = stream[i];
+	s->max_len = st::env_u64("ABG_MP_MAX_LEN", 1, abg::MP_KERNEL_MAX, s->max_len);
+	s->spill_bytes = st::env_u64("ABG_MP_SPILL_BYTES", sizeof(MPCell), MP_MAX_SPILL, s->spill_bytes);
+	s->batch = st::env_u64("ABG_MP_BATCH", 1, MP_MAX_BATCH, s->batch);
 	*out = s;
 	return ABG_OK;
 }
@@ -453,7 +402,6 @@ int abg_mp_profile_get(abg_mp* s, const char* name, double* total_ms, uint64_t* 
 {
 	if (!s || !name) return ABG_EINVAL;
 	(void)hipSetDevice(s->device);
-	prof_drain(s);
 	if (total_ms) *total_ms = 0;
 	// not kernels: the pairs whose rows the host sorted, the pairs the host aligned, the cells the kernel filled, the batches, the
 	// pairs sent out again because the arena was full
@@ -462,17 +410,13 @@ int abg_mp_profile_get(abg_mp* s, const char* name, double* total_ms, uint64_t* 
 	if (!strcmp(name, "mp_cells")) { if (launches) *launches = s->cells; return ABG_OK; }
 	if (!strcmp(name, "mp_launches")) { if (launches) *launches = s->launches; return ABG_OK; }
 	if (!strcmp(name, "mp_relaunched")) { if (launches) *launches = s->relaunched; return ABG_OK; }
-	auto it = s->prof.find(name);
-	if (total_ms) *total_ms = it == s->prof.end() ? 0 : it->second.ms;
-	if (launches) *launches = it == s->prof.end() ? 0 : it->second.launches;
-	return ABG_OK;
+	return s->prof.get(name, total_ms, launches);
 }
 
 int abg_mp_profile_reset(abg_mp* s)
 {
 	if (!s) return ABG_EINVAL;
 	(void)hipSetDevice(s->device);
-	prof_drain(s);
 	s->prof.clear();
 	s->spilled = s->host_run = s->cells = s->launches = s->relaunched = 0;
 	return ABG_OK;

@@ -11,13 +11,15 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <numeric>
 #include <string>
 #include <vector>
 
 #include "../../include/abyss_amd.h"
 #include "abg_ov.h"
+#include "abg_stage.h"
+
+namespace st = abg::stage;
 
 static_assert(sizeof(abg_ov_pair) == sizeof(abg::OVPair), "ABI struct");
 
@@ -45,8 +47,6 @@ __global__ __launch_bounds__(abg::OV_BLOCK) void ov_search_kernel(const uint64_t
 	abg::ov_search_pair(words, j, mode, top3 + 3 * (uint64_t)p, ntop + p, bits, (int)(threadIdx.x % abg::OV_WAVE));
 }
 
-struct Prof { double ms = 0; uint64_t launches = 0; };
-
 } // namespace
 
 struct abg_ov {
@@ -61,15 +61,14 @@ struct abg_ov {
 	std::vector<uint32_t> all;      // the lengths of the last all-mode call
 	std::vector<uint64_t> hbits;
 	bool profiling = false;
-	std::map<std::string, Prof> prof;
-	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
+	st::Profile prof;
 	uint64_t bytes = 0; // suffix + prefix bytes of the pairs of the profiled calls
 	std::string error;
 	~abg_ov()
 	{
 		(void)hipSetDevice(device);
 		if (stream) (void)hipStreamSynchronize(stream);
-		for (auto& e : pending) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
+		prof.drop();
 		if (words) (void)hipFree(words);
 		if (din) (void)hipFree(din);
 		if (dout) (void)hipFree(dout);
@@ -81,52 +80,6 @@ namespace {
 
 std::string g_ov_create_error;
 
-int ov_fail(abg_ov* o, hipError_t e, const char* what)
-{
-	(void)hipGetLastError();
-	o->error = std::string(what) + " failed: " + hipGetErrorString(e);
-	return e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL;
-}
-
-void prof_drain(abg_ov* o)
-{
-	for (auto& e : o->pending) {
-		float ms = 0;
-		(void)hipEventSynchronize(e.second.second);
-		if (hipEventElapsedTime(&ms, e.second.first, e.second.second) == hipSuccess) { o->prof[e.first].ms += ms; o->prof[e.first].launches++; }
-		(void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second);
-	}
-	o->pending.clear();
-}
-
-hipError_t grow(void** dev, size_t* cap, size_t need)
-{
-	if (need <= *cap) return hipSuccess;
-	if (*dev) (void)hipFree(*dev);
-	*dev = nullptr;
-	*cap = 0;
-	need += need / 4 + 4096;
-	const hipError_t e = hipMalloc(dev, need);
-	if (e == hipSuccess) *cap = need;
-	return e;
-}
-
-struct Timer {
-	abg_ov* o; const char* name; hipEvent_t a = nullptr, b = nullptr;
-	Timer(abg_ov* o_, const char* n) : o(o_), name(n)
-	{
-		if (!o->profiling) return;
-		(void)hipEventCreate(&a); (void)hipEventCreate(&b);
-		(void)hipEventRecord(a, o->stream);
-	}
-	~Timer()
-	{
-		if (!a) return;
-		(void)hipEventRecord(b, o->stream);
-		o->pending.push_back({ name, { a, b } });
-	}
-};
-
 } // namespace
 
 extern "C" {
@@ -135,20 +88,12 @@ int abg_ov_create(int device, abg_ov** out)
 {
 	if (!out) return ABG_EINVAL;
 	*out = nullptr;
-	int n = 0;
-	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); g_ov_create_error = "no HIP device available (abyss_amd has no CPU fallback)"; return ABG_ENODEV; }
-	if (device < 0 || device >= n) { g_ov_create_error = "HIP device ordinal out of range"; return ABG_ENODEV; }
+	hipStream_t stream = nullptr;
+	const int rc = st::open_device(device, "overlap searcher", g_ov_create_error, &stream, 1);
+	if (rc != ABG_OK) return rc;
 	abg_ov* o = new abg_ov;
 	o->device = device;
-	hipError_t e = hipSetDevice(device);
-	if (e == hipSuccess) e = hipStreamCreate(&o->stream);
-	if (e != hipSuccess) {
-		(void)hipGetLastError();
-		g_ov_create_error = std::string("creating the overlap searcher failed: ") + hipGetErrorString(e);
-		const int rc = e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL;
-		delete o;
-		return rc;
-	}
+	o->stream = stream;
 	if (const char* v = getenv("ABG_OV_BATCH_PAIRS")) {
 		const unsigned long long t = strtoull(v, nullptr, 10);
 		if (t > 0) o->batch_pairs = std::min<unsigned long long>(t, 1ull << 24);
@@ -196,7 +141,7 @@ int abg_ov_set_contigs(abg_ov* o, const uint8_t* bytes, const uint64_t* offsets,
 	if (e == hipSuccess && total) {
 		if ((total + 255) / 256 > 0x7FFFFFFFull) e = hipErrorInvalidValue;
 		else {
-			Timer t(o, "ov_rc");
+			st::Timed t(o->prof, o->stream, "ov_rc", o->profiling);
 			hipLaunchKernelGGL(ov_rc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, o->stream, (uint8_t*)o->words, doff, n, total);
 			e = hipGetLastError();
 		}
@@ -206,7 +151,7 @@ int abg_ov_set_contigs(abg_ov* o, const uint8_t* bytes, const uint64_t* offsets,
 	if (e != hipSuccess) {
 		if (o->words) (void)hipFree(o->words);
 		o->words = nullptr;
-		return ov_fail(o, e, "uploading the contigs");
+		return st::fail(o->error, e, "uploading the contigs");
 	}
 	o->off.assign(offsets, offsets + n + 1);
 	o->total = total;
@@ -255,27 +200,27 @@ int abg_ov_find(abg_ov* o, const abg_ov_pair* pairs, uint64_t npairs, int mode, 
 			if (o->profiling) o->bytes += 2ull * std::min(batch[i].tlen, batch[i].hlen);
 		}
 		const size_t out_bytes = mode == abg::OV_ALL ? (size_t)nbits * 8 : (size_t)nb * 16;
-		hipError_t e = grow(&o->din, &o->in_cap, nb * sizeof(abg::OVJob));
-		if (e == hipSuccess) e = grow(&o->dout, &o->out_cap, out_bytes + 8);
-		if (e != hipSuccess) { rc = ov_fail(o, e, "allocating a batch"); break; }
+		hipError_t e = st::grow_slack(&o->din, &o->in_cap, nb * sizeof(abg::OVJob));
+		if (e == hipSuccess) e = st::grow_slack(&o->dout, &o->out_cap, out_bytes + 8);
+		if (e != hipSuccess) { rc = st::fail(o->error, e, "allocating a batch"); break; }
 		e = hipMemcpyAsync(o->din, batch.data(), nb * sizeof(abg::OVJob), hipMemcpyHostToDevice, o->stream);
-		if (e != hipSuccess) { rc = ov_fail(o, e, "copying a batch to the device"); break; }
+		if (e != hipSuccess) { rc = st::fail(o->error, e, "copying a batch to the device"); break; }
 		uint32_t* dtop = (uint32_t*)o->dout;
 		uint32_t* dn = dtop + 3 * nb;
 		{
-			Timer t(o, "ov_search");
+			st::Timed t(o->prof, o->stream, "ov_search", o->profiling);
 			const unsigned per = abg::OV_BLOCK / abg::OV_WAVE;
 			hipLaunchKernelGGL(ov_search_kernel, dim3((unsigned)((nb + per - 1) / per)), dim3(abg::OV_BLOCK), 0, o->stream, o->words,
 			    (const abg::OVJob*)o->din, (uint32_t)nb, mode, dtop, dn, (uint64_t*)o->dout);
 			e = hipGetLastError();
 		}
-		if (e != hipSuccess) { rc = ov_fail(o, e, "launching the search"); break; }
+		if (e != hipSuccess) { rc = st::fail(o->error, e, "launching the search"); break; }
 		if (mode == abg::OV_TOP) {
 			htop.resize(3 * nb); hn.resize(nb);
 			e = hipMemcpyAsync(htop.data(), dtop, nb * 12, hipMemcpyDeviceToHost, o->stream);
 			if (e == hipSuccess) e = hipMemcpyAsync(hn.data(), dn, nb * 4, hipMemcpyDeviceToHost, o->stream);
 			if (e == hipSuccess) e = hipStreamSynchronize(o->stream);
-			if (e != hipSuccess) { rc = ov_fail(o, e, "the search"); break; }
+			if (e != hipSuccess) { rc = st::fail(o->error, e, "the search"); break; }
 			for (uint64_t i = 0; i < nb; ++i) {
 				memcpy(top3 + 3 * order[a + i], htop.data() + 3 * i, 12);
 				ntop[order[a + i]] = hn[i];
@@ -284,7 +229,7 @@ int abg_ov_find(abg_ov* o, const abg_ov_pair* pairs, uint64_t npairs, int mode, 
 			o->hbits.resize(nbits);
 			if (nbits) e = hipMemcpyAsync(o->hbits.data(), o->dout, nbits * 8, hipMemcpyDeviceToHost, o->stream);
 			if (e == hipSuccess) e = hipStreamSynchronize(o->stream);
-			if (e != hipSuccess) { rc = ov_fail(o, e, "the search"); break; }
+			if (e != hipSuccess) { rc = st::fail(o->error, e, "the search"); break; }
 			for (uint64_t i = 0; i < nb; ++i) abg::ov_expand(o->hbits.data() + batch[i].bits, batch[i].tlen, batch[i].hlen, found[order[a + i]]);
 		}
 	}
@@ -310,16 +255,12 @@ int abg_ov_profile_get(abg_ov* o, const char* name, double* total_ms, uint64_t* 
 {
 	if (!o || !name) return ABG_EINVAL;
 	(void)hipSetDevice(o->device);
-	prof_drain(o);
 	if (!strcmp(name, "ov_search_bytes")) { // not a kernel: 2 min(|t|, |h|) summed over the pairs of the profiled calls, as `launches`
 		if (total_ms) *total_ms = 0;
 		if (launches) *launches = o->bytes;
 		return ABG_OK;
 	}
-	auto it = o->prof.find(name);
-	if (total_ms) *total_ms = it == o->prof.end() ? 0 : it->second.ms;
-	if (launches) *launches = it == o->prof.end() ? 0 : it->second.launches;
-	return ABG_OK;
+	return o->prof.get(name, total_ms, launches);
 }
 
 } // extern "C"

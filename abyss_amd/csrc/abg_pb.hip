@@ -22,12 +22,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/abyss_amd.h"
 #include "abg_pb.h"
+#include "abg_stage.h"
+
+namespace st = abg::stage;
 
 namespace {
 
@@ -138,8 +140,6 @@ __global__ __launch_bounds__(64) void pb_wave_kernel(const PBPair* __restrict__ 
 	}
 }
 
-struct Prof { double ms = 0; uint64_t launches = 0; };
-
 } // namespace
 
 struct abg_pb {
@@ -152,15 +152,14 @@ struct abg_pb {
 	void* d_arena = nullptr; size_t arena_cap = 0;
 	void* d_rows = nullptr; size_t rows_cap = 0;
 	std::vector<uint8_t> cons;                      // the answer of the last call
-	std::map<std::string, Prof> prof;
-	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
+	st::Profile prof;
 	uint64_t redone = 0, cells = 0, launches = 0;
 	std::string error;
 	~abg_pb()
 	{
 		(void)hipSetDevice(device);
 		if (stream) (void)hipStreamSynchronize(stream);
-		for (auto& e : pending) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
+		prof.drop();
 		for (void* p : { d_in, d_cons[0], d_cons[1], d_meta, d_arena, d_rows })
 			if (p) (void)hipFree(p);
 		if (stream) (void)hipStreamDestroy(stream);
@@ -170,51 +169,6 @@ struct abg_pb {
 namespace {
 
 std::string g_pb_create_error;
-
-int pb_fail(abg_pb* s, hipError_t e, const char* what)
-{
-	(void)hipGetLastError();
-	s->error = std::string(what) + " failed: " + hipGetErrorString(e);
-	return e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL;
-}
-
-void prof_drain(abg_pb* s)
-{
-	for (auto& e : s->pending) {
-		float ms = 0;
-		(void)hipEventSynchronize(e.second.second);
-		if (hipEventElapsedTime(&ms, e.second.first, e.second.second) == hipSuccess) { s->prof[e.first].ms += ms; s->prof[e.first].launches++; }
-		(void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second);
-	}
-	s->pending.clear();
-}
-
-hipError_t grow(void** dev, size_t* cap, size_t need)
-{
-	if (need <= *cap) return hipSuccess;
-	if (*dev) (void)hipFree(*dev);
-	*dev = nullptr;
-	*cap = 0;
-	const hipError_t e = hipMalloc(dev, need);
-	if (e == hipSuccess) *cap = need;
-	return e;
-}
-
-unsigned long long env_u64(const char* name, unsigned long long lo, unsigned long long hi, unsigned long long dflt)
-{
-	const char* v = getenv(name);
-	if (!v || !*v) return dflt;
-	const unsigned long long t = strtoull(v, nullptr, 10);
-	return std::max(lo, std::min(hi, t));
-}
-
-size_t up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-struct Timed {
-	abg_pb* s; const char* name; hipEvent_t t0 = nullptr, t1 = nullptr;
-	Timed(abg_pb* s, const char* name) : s(s), name(name) { (void)hipEventCreate(&t0); (void)hipEventCreate(&t1); (void)hipEventRecord(t0, s->stream); }
-	~Timed() { (void)hipEventRecord(t1, s->stream); s->pending.push_back({ name, { t0, t1 } }); }
-};
 
 constexpr uint64_t PB_MAX_ARENA = 1ull << 40;
 
@@ -240,7 +194,7 @@ int pb_run(abg_pb* s, std::vector<PBPair>& pairs, const uint8_t* h_in, const uin
 			cells += c;
 			const bool lane = p.la == 0 || p.lb == 0 || std::max(p.la, p.lb) <= s->small_limit;
 			if (lane) small.push_back((uint32_t)(end - q));
-			else { p.row_off = rows; rows += up(p.lb, 64); large.push_back((uint32_t)(end - q)); }
+			else { p.row_off = rows; rows += st::up(p.lb, 64); large.push_back((uint32_t)(end - q)); }
 		}
 		if (end == q) { // the pair at q fits no arena: the host's, by the same header
 			PBPair& p = pairs[q];
@@ -248,13 +202,13 @@ int pb_run(abg_pb* s, std::vector<PBPair>& pairs, const uint8_t* h_in, const uin
 			if (p.a_src) {
 				ha.resize(p.la);
 				const hipError_t e = p.la ? hipMemcpy(ha.data(), d_prev + p.a_off, p.la, hipMemcpyDeviceToHost) : hipSuccess;
-				if (e != hipSuccess) return pb_fail(s, e, "fetching a consensus");
+				if (e != hipSuccess) return st::fail(s->error, e, "fetching a consensus");
 				a = ha.data();
 			}
 			abg::pb_align_host(a, p.la, h_in + p.b_off, p.lb, matches[q], sizes[q], d_out ? &hc : nullptr);
 			if (d_out && !hc.empty()) {
 				const hipError_t e = hipMemcpy(d_out + p.cons_off + p.la + p.lb - hc.size(), hc.data(), hc.size(), hipMemcpyHostToDevice);
-				if (e != hipSuccess) return pb_fail(s, e, "storing a consensus");
+				if (e != hipSuccess) return st::fail(s->error, e, "storing a consensus");
 			}
 			redone[q] = 1;
 			s->redone++;
@@ -262,38 +216,38 @@ int pb_run(abg_pb* s, std::vector<PBPair>& pairs, const uint8_t* h_in, const uin
 			continue;
 		}
 		const uint64_t nb = end - q;
-		const size_t pairs_at = 0, small_at = up(nb * sizeof(PBPair), 64), large_at = small_at + up(small.size() * 4, 64), m_at = large_at + up(large.size() * 4, 64),
-		             s_at = m_at + up(nb * 4, 64), meta_bytes = s_at + up(nb * 4, 64);
-		hipError_t e = grow(&s->d_meta, &s->meta_cap, meta_bytes);
-		if (e == hipSuccess) e = grow(&s->d_arena, &s->arena_cap, std::max<uint64_t>(cells, 64));
-		if (e == hipSuccess) e = grow(&s->d_rows, &s->rows_cap, std::max<uint64_t>(rows * sizeof(int2), 64));
-		if (e != hipSuccess) return pb_fail(s, e, "allocating a launch");
+		const size_t pairs_at = 0, small_at = st::up(nb * sizeof(PBPair), 64), large_at = small_at + st::up(small.size() * 4, 64), m_at = large_at + st::up(large.size() * 4, 64),
+		             s_at = m_at + st::up(nb * 4, 64), meta_bytes = s_at + st::up(nb * 4, 64);
+		hipError_t e = st::grow(&s->d_meta, &s->meta_cap, meta_bytes);
+		if (e == hipSuccess) e = st::grow(&s->d_arena, &s->arena_cap, std::max<uint64_t>(cells, 64));
+		if (e == hipSuccess) e = st::grow(&s->d_rows, &s->rows_cap, std::max<uint64_t>(rows * sizeof(int2), 64));
+		if (e != hipSuccess) return st::fail(s->error, e, "allocating a launch");
 		char* meta = (char*)s->d_meta;
 		e = hipMemcpyAsync(meta + pairs_at, &pairs[q], nb * sizeof(PBPair), hipMemcpyHostToDevice, s->stream);
 		if (e == hipSuccess && !small.empty()) e = hipMemcpyAsync(meta + small_at, small.data(), small.size() * 4, hipMemcpyHostToDevice, s->stream);
 		if (e == hipSuccess && !large.empty()) e = hipMemcpyAsync(meta + large_at, large.data(), large.size() * 4, hipMemcpyHostToDevice, s->stream);
-		if (e != hipSuccess) return pb_fail(s, e, "copying a launch to the device");
+		if (e != hipSuccess) return st::fail(s->error, e, "copying a launch to the device");
 		if (!small.empty()) {
-			Timed t(s, "pb_lane");
+			st::Timed t(s->prof, s->stream, "pb_lane");
 			hipLaunchKernelGGL(pb_lane_kernel, dim3((unsigned)((small.size() + 63) / 64)), dim3(64), 0, s->stream, (const PBPair*)(meta + pairs_at),
 			    (const uint32_t*)(meta + small_at), (uint32_t)small.size(), (const uint8_t*)s->d_in, d_prev, (uint8_t*)s->d_arena, d_out, (uint32_t*)(meta + m_at),
 			    (uint32_t*)(meta + s_at));
 			e = hipGetLastError();
 		}
 		if (e == hipSuccess && !large.empty()) {
-			Timed t(s, "pb_wave");
+			st::Timed t(s->prof, s->stream, "pb_wave");
 			hipLaunchKernelGGL(pb_wave_kernel, dim3((unsigned)large.size()), dim3(64), 0, s->stream, (const PBPair*)(meta + pairs_at), (const uint32_t*)(meta + large_at),
 			    (const uint8_t*)s->d_in, d_prev, (uint8_t*)s->d_arena, (int2*)s->d_rows, d_out, (uint32_t*)(meta + m_at), (uint32_t*)(meta + s_at));
 			e = hipGetLastError();
 		}
-		if (e != hipSuccess) return pb_fail(s, e, "launching the alignment");
+		if (e != hipSuccess) return st::fail(s->error, e, "launching the alignment");
 		e = hipMemcpyAsync(matches + q, meta + m_at, nb * 4, hipMemcpyDeviceToHost, s->stream);
 		if (e == hipSuccess) e = hipMemcpyAsync(sizes + q, meta + s_at, nb * 4, hipMemcpyDeviceToHost, s->stream);
 		if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-		if (e != hipSuccess) return pb_fail(s, e, "the alignment");
+		if (e != hipSuccess) return st::fail(s->error, e, "the alignment");
 		for (uint64_t i = q; i < end; ++i) { redone[i] = 0; s->cells += (uint64_t)pairs[i].la * pairs[i].lb; }
 		s->launches++;
-		if (s->pending.size() >= 64) prof_drain(s);
+		s->prof.drain_if(64);
 		q = end;
 	}
 	return ABG_OK;
@@ -325,21 +279,13 @@ int abg_pb_create(int device, abg_pb** out)
 {
 	if (!out) return ABG_EINVAL;
 	*out = nullptr;
-	int n = 0;
-	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); g_pb_create_error = "no HIP device available (abyss_amd has no CPU fallback)"; return ABG_ENODEV; }
-	if (device < 0 || device >= n) { g_pb_create_error = "HIP device ordinal out of range"; return ABG_ENODEV; }
+	hipStream_t stream = nullptr;
+	const int rc = st::open_device(device, "bubble aligner", g_pb_create_error, &stream, 1);
+	if (rc != ABG_OK) return rc;
 	abg_pb* s = new abg_pb;
 	s->device = device;
-	hipError_t e = hipSetDevice(device);
-	if (e == hipSuccess) e = hipStreamCreate(&s->stream);
-	if (e != hipSuccess) {
-		(void)hipGetLastError();
-		g_pb_create_error = std::string("creating the bubble aligner failed: ") + hipGetErrorString(e);
-		const int rc = e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL;
-		delete s;
-		return rc;
-	}
-	s->arena_bytes = env_u64("ABG_PB_ARENA_BYTES", 4, PB_MAX_ARENA, s->arena_bytes);
+	s->stream = stream;
+	s->arena_bytes = st::env_u64("ABG_PB_ARENA_BYTES", 4, PB_MAX_ARENA, s->arena_bytes);
 	*out = s;
 	return ABG_OK;
 }
@@ -382,17 +328,17 @@ int abg_pb_align(abg_pb* s, uint64_t n, const uint8_t* a, const uint64_t* a_offs
 		pairs[i] = PBPair{ a_offsets[i], na + b_offsets[i], 0, 0, cap, (uint32_t)(a_offsets[i + 1] - a_offsets[i]), (uint32_t)(b_offsets[i + 1] - b_offsets[i]), 0, 0 };
 		cap += (uint64_t)pairs[i].la + pairs[i].lb;
 	}
-	hipError_t e = grow(&s->d_in, &s->in_cap, std::max<uint64_t>(in.size(), 64));
-	if (e == hipSuccess && want_consensus) e = grow(&s->d_cons[0], &s->cons_cap[0], std::max<uint64_t>(cap, 64));
+	hipError_t e = st::grow(&s->d_in, &s->in_cap, std::max<uint64_t>(in.size(), 64));
+	if (e == hipSuccess && want_consensus) e = st::grow(&s->d_cons[0], &s->cons_cap[0], std::max<uint64_t>(cap, 64));
 	if (e == hipSuccess && !in.empty()) e = hipMemcpyAsync(s->d_in, in.data(), in.size(), hipMemcpyHostToDevice, s->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-	if (e != hipSuccess) return pb_fail(s, e, "uploading the pairs");
+	if (e != hipSuccess) return st::fail(s->error, e, "uploading the pairs");
 	const int rc = pb_run(s, pairs, in.data(), nullptr, want_consensus ? (uint8_t*)s->d_cons[0] : nullptr, matches, size, redone);
 	if (rc != ABG_OK) return rc;
 	if (want_consensus) {
 		std::vector<uint8_t> all(cap);
 		if (cap) e = hipMemcpy(all.data(), s->d_cons[0], cap, hipMemcpyDeviceToHost);
-		if (e != hipSuccess) return pb_fail(s, e, "fetching the consensuses");
+		if (e != hipSuccess) return st::fail(s->error, e, "fetching the consensuses");
 		for (uint64_t i = 0; i < n; ++i) {
 			const uint8_t* end = all.data() + pairs[i].cons_off + pairs[i].la + pairs[i].lb;
 			s->cons.insert(s->cons.end(), end - size[i], end);
@@ -424,9 +370,9 @@ int abg_pb_align_chain(abg_pb* s, uint64_t ngroups, const uint64_t* group_first,
 	const uint64_t total = offsets[nbranches];
 	if ((total && !bytes) || !pb_valid(s, bytes, total, "bytes")) return ABG_EINVAL;
 	(void)hipSetDevice(s->device);
-	hipError_t e = grow(&s->d_in, &s->in_cap, std::max<uint64_t>(total, 64));
+	hipError_t e = st::grow(&s->d_in, &s->in_cap, std::max<uint64_t>(total, 64));
 	if (e == hipSuccess && total) e = hipMemcpy(s->d_in, bytes, total, hipMemcpyHostToDevice);
-	if (e != hipSuccess) return pb_fail(s, e, "uploading the branches");
+	if (e != hipSuccess) return st::fail(s->error, e, "uploading the branches");
 	// where each group's consensus of the round before starts, and its length; its matches so far
 	std::vector<uint64_t> cur_off(ngroups);
 	std::vector<uint32_t> cur_len(ngroups), acc(ngroups, 0), m, sz;
@@ -452,8 +398,8 @@ int abg_pb_align_chain(abg_pb* s, uint64_t ngroups, const uint64_t* group_first,
 			finishing = finishing || nb == r + 2;
 		}
 		void*& out = s->d_cons[r & 1];
-		e = grow(&out, &s->cons_cap[r & 1], std::max<uint64_t>(cap, 64));
-		if (e != hipSuccess) return pb_fail(s, e, "allocating a round");
+		e = st::grow(&out, &s->cons_cap[r & 1], std::max<uint64_t>(cap, 64));
+		if (e != hipSuccess) return st::fail(s->error, e, "allocating a round");
 		m.assign(pairs.size(), 0);
 		sz.assign(pairs.size(), 0);
 		rd.assign(pairs.size(), 0);
@@ -462,7 +408,7 @@ int abg_pb_align_chain(abg_pb* s, uint64_t ngroups, const uint64_t* group_first,
 		if (finishing) {
 			all.resize(cap);
 			e = cap ? hipMemcpy(all.data(), out, cap, hipMemcpyDeviceToHost) : hipSuccess;
-			if (e != hipSuccess) return pb_fail(s, e, "fetching the consensuses");
+			if (e != hipSuccess) return st::fail(s->error, e, "fetching the consensuses");
 		}
 		for (size_t i = 0; i < pairs.size(); ++i) {
 			const uint64_t g = who[i], nb = group_first[g + 1] - group_first[g];
@@ -489,23 +435,18 @@ int abg_pb_profile_get(abg_pb* s, const char* name, double* total_ms, uint64_t* 
 {
 	if (!s || !name) return ABG_EINVAL;
 	(void)hipSetDevice(s->device);
-	prof_drain(s);
 	if (total_ms) *total_ms = 0;
 	// not kernels: the pairs aligned on the host, the cells the kernels filled, the launches (one of each kernel at the most)
 	if (!strcmp(name, "pb_redone")) { if (launches) *launches = s->redone; return ABG_OK; }
 	if (!strcmp(name, "pb_cells")) { if (launches) *launches = s->cells; return ABG_OK; }
 	if (!strcmp(name, "pb_launches")) { if (launches) *launches = s->launches; return ABG_OK; }
-	auto it = s->prof.find(name);
-	if (total_ms) *total_ms = it == s->prof.end() ? 0 : it->second.ms;
-	if (launches) *launches = it == s->prof.end() ? 0 : it->second.launches;
-	return ABG_OK;
+	return s->prof.get(name, total_ms, launches);
 }
 
 int abg_pb_profile_reset(abg_pb* s)
 {
 	if (!s) return ABG_EINVAL;
 	(void)hipSetDevice(s->device);
-	prof_drain(s);
 	s->prof.clear();
 	s->redone = s->cells = s->launches = 0;
 	return ABG_OK;

@@ -19,13 +19,15 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/abyss_amd.h"
 #include "abg_rr.h"
+#include "abg_stage.h"
+
+namespace st = abg::stage;
 
 namespace {
 
@@ -103,8 +105,6 @@ __global__ void __launch_bounds__(256) k_rr_popcount(const uint4* __restrict__ w
 	if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
 }
 
-struct Prof { double ms = 0; uint64_t launches = 0; };
-
 } // namespace
 
 struct abg_rr {
@@ -125,14 +125,13 @@ struct abg_rr {
 	unsigned long long* d_count = nullptr;
 	uint32_t cus = 256;
 	bool profiling = false;
-	std::map<std::string, Prof> prof;
-	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
+	st::Profile prof;
 	std::string error;
 	~abg_rr()
 	{
 		(void)hipSetDevice(device);
 		if (stream) (void)hipStreamSynchronize(stream);
-		for (auto& e : pending) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
+		prof.drop();
 		for (int i = 0; i < 2; i++) {
 			if (pin[i]) (void)hipHostFree(pin[i]);
 			if (dev[i]) (void)hipFree(dev[i]);
@@ -149,41 +148,6 @@ namespace {
 
 std::string g_rr_create_error;
 
-bool rr_ok(abg_rr* f, hipError_t e, const char* what)
-{
-	if (e == hipSuccess) return true;
-	(void)hipGetLastError();
-	f->error = std::string(what) + " failed: " + hipGetErrorString(e);
-	return false;
-}
-int rr_code_of(hipError_t e) { return e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL; }
-
-struct Timed { // brackets one launch with events when profiling
-	abg_rr* f; const char* name; hipEvent_t a = nullptr, b = nullptr;
-	Timed(abg_rr* f, const char* name) : f(f), name(name)
-	{
-		if (!f->profiling) return;
-		(void)hipEventCreate(&a); (void)hipEventCreate(&b);
-		(void)hipEventRecord(a, f->stream);
-	}
-	~Timed()
-	{
-		if (!a) return;
-		(void)hipEventRecord(b, f->stream);
-		f->pending.push_back({ name, { a, b } });
-	}
-};
-void prof_drain(abg_rr* f)
-{
-	for (auto& e : f->pending) {
-		float ms = 0;
-		(void)hipEventSynchronize(e.second.second);
-		if (hipEventElapsedTime(&ms, e.second.first, e.second.second) == hipSuccess) { f->prof[e.first].ms += ms; f->prof[e.first].launches++; }
-		(void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second);
-	}
-	f->pending.clear();
-}
-
 // packs records [a, b) of the caller's reads into a staging slot: the first `span` characters, the rest of the row 'N'
 void pack_rows(char* dst, uint32_t stride, uint32_t span, const char* seqs, const uint64_t* offsets, const uint64_t* rows, uint64_t a, uint64_t b)
 {
@@ -198,7 +162,7 @@ void pack_rows(char* dst, uint32_t stride, uint32_t span, const char* seqs, cons
 
 int launch_insert(abg_rr* f, int slot, uint32_t stride, uint32_t span, uint64_t n)
 {
-	Timed t(f, "rr_insert");
+	st::Timed t(f->prof, f->stream, "rr_insert", f->profiling);
 	const uint32_t lw = stride / 4 + 1;
 	const uint32_t grid_cap = f->cus * 8;
 	auto grid = [&](int threads) { return (unsigned)std::min<uint64_t>((n + threads - 1) / threads, grid_cap); };
@@ -211,7 +175,7 @@ int launch_insert(abg_rr* f, int slot, uint32_t stride, uint32_t span, uint64_t 
 	else
 		k_rr_insert_direct<<<grid(256), 256, 0, f->stream>>>(f->p, (const unsigned char*)f->dev[slot], stride, span, n, f->bits);
 	const hipError_t e = hipGetLastError();
-	if (!rr_ok(f, e, "the insert kernel launch")) return rr_code_of(e);
+	if (e != hipSuccess) return st::fail(f->error, e, "the insert kernel launch");
 	return ABG_OK;
 }
 
@@ -224,18 +188,17 @@ int abg_rr_create(int device, uint64_t bytes, uint32_t hash_num, uint32_t r, abg
 	if (!out) return ABG_EINVAL;
 	*out = nullptr;
 	if (bytes == 0 || hash_num == 0 || hash_num > abg::RR_MAX_HASHES || r == 0) { g_rr_create_error = "bad filter size, hash count or r"; return ABG_EINVAL; }
-	int n = 0;
-	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); g_rr_create_error = "no HIP device available (abyss_amd has no CPU fallback)"; return ABG_ENODEV; }
-	if (device < 0 || device >= n) { g_rr_create_error = "HIP device ordinal out of range"; return ABG_ENODEV; }
+	hipStream_t stream = nullptr;
+	const int opened = st::open_device(device, "read filter", g_rr_create_error, &stream, 1);
+	if (opened != ABG_OK) return opened;
 	abg_rr* f = new abg_rr;
 	f->device = device;
+	f->stream = stream;
 	f->bytes = (bytes + 7) / 8 * 8; // btllib::BloomFilter rounds its size up to whole 64-bit words
 	f->p = abg::make_rr_params(r, hash_num, f->bytes);
-	hipError_t e = hipSetDevice(device);
 	hipDeviceProp_t prop;
-	if (e == hipSuccess && hipGetDeviceProperties(&prop, device) == hipSuccess) f->cus = (uint32_t)prop.multiProcessorCount;
-	if (e == hipSuccess) e = hipStreamCreate(&f->stream);
-	if (e == hipSuccess) e = hipMalloc((void**)&f->bits, (f->bytes + 15) / 16 * 16);
+	if (hipGetDeviceProperties(&prop, device) == hipSuccess) f->cus = (uint32_t)prop.multiProcessorCount;
+	hipError_t e = hipMalloc((void**)&f->bits, (f->bytes + 15) / 16 * 16);
 	if (e == hipSuccess) e = hipMemsetAsync(f->bits, 0, (f->bytes + 15) / 16 * 16, f->stream);
 	if (e == hipSuccess) e = hipMalloc((void**)&f->d_count, 8);
 	for (int i = 0; i < 2 && e == hipSuccess; i++) {
@@ -244,9 +207,7 @@ int abg_rr_create(int device, uint64_t bytes, uint32_t hash_num, uint32_t r, abg
 		if (e == hipSuccess) e = hipEventCreateWithFlags(&f->done[i], hipEventDisableTiming);
 	}
 	if (e != hipSuccess) {
-		(void)hipGetLastError();
-		g_rr_create_error = std::string("creating the read filter failed: ") + hipGetErrorString(e);
-		const int rc = rr_code_of(e);
+		const int rc = st::create_fail(g_rr_create_error, e, "read filter");
 		delete f;
 		return rc;
 	}
@@ -269,7 +230,7 @@ int abg_rr_clear(abg_rr* f)
 	if (!f) return ABG_EINVAL;
 	(void)hipSetDevice(f->device);
 	const hipError_t e = hipMemsetAsync(f->bits, 0, (f->bytes + 15) / 16 * 16, f->stream);
-	return rr_ok(f, e, "clearing the filter") ? ABG_OK : rr_code_of(e);
+	return e == hipSuccess ? ABG_OK : st::fail(f->error, e, "clearing the filter");
 }
 
 int abg_rr_insert_seqs(abg_rr* f, const char* seqs, const uint64_t* offsets, uint64_t n, uint32_t max_bases, const uint32_t* lengths,
@@ -297,7 +258,7 @@ int abg_rr_insert_seqs(abg_rr* f, const char* seqs, const uint64_t* offsets, uin
 		f->next ^= 1;
 		if (f->busy[s]) {
 			const hipError_t e = hipEventSynchronize(f->done[s]);
-			if (!rr_ok(f, e, "waiting for a staging slot")) return rr_code_of(e);
+			if (e != hipSuccess) return st::fail(f->error, e, "waiting for a staging slot");
 			f->busy[s] = false;
 		}
 		{
@@ -312,11 +273,11 @@ int abg_rr_insert_seqs(abg_rr* f, const char* seqs, const uint64_t* offsets, uin
 			for (auto& th : pool) th.join();
 		}
 		hipError_t e = hipMemcpyAsync(f->dev[s], f->pin[s], cnt * stride, hipMemcpyHostToDevice, f->stream);
-		if (!rr_ok(f, e, "copying reads to the device")) return rr_code_of(e);
+		if (e != hipSuccess) return st::fail(f->error, e, "copying reads to the device");
 		const int rc = launch_insert(f, s, stride, span, cnt);
 		if (rc != ABG_OK) return rc;
 		e = hipEventRecord(f->done[s], f->stream);
-		if (!rr_ok(f, e, "hipEventRecord")) return rr_code_of(e);
+		if (e != hipSuccess) return st::fail(f->error, e, "hipEventRecord");
 		f->busy[s] = true;
 	}
 	return ABG_OK;
@@ -333,7 +294,7 @@ int abg_rr_contains_seqs(abg_rr* f, const char* seqs, const uint64_t* offsets, u
 		if (f->qdev) { (void)hipStreamSynchronize(f->stream); (void)hipFree(f->qdev); f->qdev = nullptr; f->qcap = 0; }
 		const size_t cap = std::max<size_t>(need, 1u << 20);
 		const hipError_t e = hipMalloc(&f->qdev, cap);
-		if (!rr_ok(f, e, "device memory for the queries")) return rr_code_of(e);
+		if (e != hipSuccess) return st::fail(f->error, e, "device memory for the queries");
 		f->qcap = cap;
 	}
 	char* base = (char*)f->qdev;
@@ -341,17 +302,17 @@ int abg_rr_contains_seqs(abg_rr* f, const char* seqs, const uint64_t* offsets, u
 	for (uint64_t i = 0; i <= n; i++) rel[i] = offsets[i] - a;
 	hipError_t e = hipMemcpyAsync(base, seqs + a, total, hipMemcpyHostToDevice, f->stream);
 	if (e == hipSuccess) e = hipMemcpyAsync(base + off_at, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, f->stream);
-	if (!rr_ok(f, e, "copying the queries to the device")) return rr_code_of(e);
+	if (e != hipSuccess) return st::fail(f->error, e, "copying the queries to the device");
 	{
-		Timed t(f, "rr_contains");
+		st::Timed t(f->prof, f->stream, "rr_contains", f->profiling);
 		const unsigned grid = (unsigned)std::min<uint64_t>((n + 3) / 4, (uint64_t)f->cus * 8);
 		k_rr_contains<<<grid, 256, 0, f->stream>>>(f->p, (const unsigned char*)base, (const uint64_t*)(base + off_at), n, f->bits, (uint32_t*)(base + cnt_at));
 		e = hipGetLastError();
-		if (!rr_ok(f, e, "the query kernel launch")) return rr_code_of(e);
+		if (e != hipSuccess) return st::fail(f->error, e, "the query kernel launch");
 	}
 	e = hipMemcpyAsync(found, base + cnt_at, n * 4, hipMemcpyDeviceToHost, f->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(f->stream); // (also keeps `rel` alive until its copy is done)
-	if (!rr_ok(f, e, "reading the counts back")) return rr_code_of(e);
+	if (e != hipSuccess) return st::fail(f->error, e, "reading the counts back");
 	return ABG_OK;
 }
 
@@ -361,7 +322,7 @@ int abg_rr_popcount(abg_rr* f, uint64_t* bits_set)
 	(void)hipSetDevice(f->device);
 	hipError_t e = hipMemsetAsync(f->d_count, 0, 8, f->stream);
 	if (e == hipSuccess) {
-		Timed t(f, "rr_popcount");
+		st::Timed t(f->prof, f->stream, "rr_popcount", f->profiling);
 		const uint64_t n16 = (f->bytes + 15) / 16;
 		k_rr_popcount<<<(unsigned)std::min<uint64_t>((n16 + 255) / 256, (uint64_t)f->cus * 8), 256, 0, f->stream>>>((const uint4*)f->bits, n16, f->d_count);
 		e = hipGetLastError();
@@ -369,7 +330,7 @@ int abg_rr_popcount(abg_rr* f, uint64_t* bits_set)
 	unsigned long long c = 0;
 	if (e == hipSuccess) e = hipMemcpyAsync(&c, f->d_count, 8, hipMemcpyDeviceToHost, f->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
-	if (!rr_ok(f, e, "counting the filter's bits")) return rr_code_of(e);
+	if (e != hipSuccess) return st::fail(f->error, e, "counting the filter's bits");
 	*bits_set = c;
 	return ABG_OK;
 }
@@ -380,7 +341,7 @@ int abg_rr_export(abg_rr* f, uint8_t* host_out)
 	(void)hipSetDevice(f->device);
 	hipError_t e = hipMemcpyAsync(host_out, f->bits, f->bytes, hipMemcpyDeviceToHost, f->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
-	return rr_ok(f, e, "copying the filter to the host") ? ABG_OK : rr_code_of(e);
+	return e == hipSuccess ? ABG_OK : st::fail(f->error, e, "copying the filter to the host");
 }
 
 int abg_rr_sync(abg_rr* f)
@@ -389,7 +350,7 @@ int abg_rr_sync(abg_rr* f)
 	(void)hipSetDevice(f->device);
 	const hipError_t e = hipStreamSynchronize(f->stream);
 	f->busy[0] = f->busy[1] = false;
-	return rr_ok(f, e, "hipStreamSynchronize") ? ABG_OK : rr_code_of(e);
+	return e == hipSuccess ? ABG_OK : st::fail(f->error, e, "hipStreamSynchronize");
 }
 
 int abg_rr_profile(abg_rr* f, int on)
@@ -402,11 +363,7 @@ int abg_rr_profile_get(abg_rr* f, const char* name, double* total_ms, uint64_t* 
 {
 	if (!f || !name) return ABG_EINVAL;
 	(void)hipSetDevice(f->device);
-	prof_drain(f);
-	auto it = f->prof.find(name);
-	if (total_ms) *total_ms = it == f->prof.end() ? 0 : it->second.ms;
-	if (launches) *launches = it == f->prof.end() ? 0 : it->second.launches;
-	return ABG_OK;
+	return f->prof.get(name, total_ms, launches);
 }
 
 } // extern "C"

@@ -16,12 +16,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/abyss_amd.h"
 #include "abg_sg.h"
+#include "abg_stage.h"
+
+namespace st = abg::stage;
 
 namespace {
 
@@ -96,8 +98,6 @@ __global__ __launch_bounds__(64) void sg_search_kernel(abg::SGGraph g, const abg
 	if (count_busy && steps) { atomicAdd(&counters[1], thin); atomicAdd(&counters[2], steps); }
 }
 
-struct Prof { double ms = 0; uint64_t launches = 0; };
-
 } // namespace
 
 struct abg_sg {
@@ -119,8 +119,7 @@ struct abg_sg {
 	std::vector<uint64_t> path_off;
 	std::vector<uint32_t> nodes;
 	int profiling = 0; // 1: events around the launches; 2: the kernel also counts its wave steps
-	std::map<std::string, Prof> prof;
-	std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
+	st::Profile prof;
 	uint64_t thin_steps = 0, all_steps = 0, redone = 0;
 	std::string error;
 	void free_graph()
@@ -137,7 +136,7 @@ struct abg_sg {
 	{
 		(void)hipSetDevice(device);
 		if (stream) (void)hipStreamSynchronize(stream);
-		for (auto& e : pending) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
+		prof.drop();
 		free_graph();
 		if (din) (void)hipFree(din);
 		if (dstack) (void)hipFree(dstack);
@@ -150,43 +149,6 @@ struct abg_sg {
 namespace {
 
 std::string g_sg_create_error;
-
-int sg_fail(abg_sg* s, hipError_t e, const char* what)
-{
-	(void)hipGetLastError();
-	s->error = std::string(what) + " failed: " + hipGetErrorString(e);
-	return e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL;
-}
-
-void prof_drain(abg_sg* s)
-{
-	for (auto& e : s->pending) {
-		float ms = 0;
-		(void)hipEventSynchronize(e.second.second);
-		if (hipEventElapsedTime(&ms, e.second.first, e.second.second) == hipSuccess) { s->prof[e.first].ms += ms; s->prof[e.first].launches++; }
-		(void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second);
-	}
-	s->pending.clear();
-}
-
-hipError_t grow(void** dev, size_t* cap, size_t need)
-{
-	if (need <= *cap) return hipSuccess;
-	if (*dev) (void)hipFree(*dev);
-	*dev = nullptr;
-	*cap = 0;
-	const hipError_t e = hipMalloc(dev, need);
-	if (e == hipSuccess) *cap = need;
-	return e;
-}
-
-unsigned long long env_u64(const char* name, unsigned long long lo, unsigned long long hi, unsigned long long dflt)
-{
-	const char* v = getenv(name);
-	if (!v || !*v) return dflt;
-	const unsigned long long t = strtoull(v, nullptr, 10);
-	return std::max(lo, std::min(hi, t));
-}
 
 template <class T> hipError_t upload(T** dev, const std::vector<T>& host, hipStream_t stream)
 {
@@ -203,25 +165,17 @@ int abg_sg_create(int device, abg_sg** out)
 {
 	if (!out) return ABG_EINVAL;
 	*out = nullptr;
-	int n = 0;
-	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); g_sg_create_error = "no HIP device available (abyss_amd has no CPU fallback)"; return ABG_ENODEV; }
-	if (device < 0 || device >= n) { g_sg_create_error = "HIP device ordinal out of range"; return ABG_ENODEV; }
+	hipStream_t stream = nullptr;
+	const int rc = st::open_device(device, "path searcher", g_sg_create_error, &stream, 1);
+	if (rc != ABG_OK) return rc;
 	abg_sg* s = new abg_sg;
 	s->device = device;
-	hipError_t e = hipSetDevice(device);
-	if (e == hipSuccess) e = hipStreamCreate(&s->stream);
-	if (e != hipSuccess) {
-		(void)hipGetLastError();
-		g_sg_create_error = std::string("creating the path searcher failed: ") + hipGetErrorString(e);
-		const int rc = e == hipErrorOutOfMemory ? ABG_ENOMEM : ABG_EINTERNAL;
-		delete s;
-		return rc;
-	}
-	s->batch = env_u64("ABG_SG_BATCH", 1, 1ull << 24, s->batch);
-	s->stack_depth = (uint32_t)env_u64("ABG_SG_STACK_DEPTH", 1, 1u << 16, s->stack_depth);
-	s->max_constraints = (uint32_t)env_u64("ABG_SG_MAX_CONSTRAINTS", 1, abg::SG_MAX_CONSTRAINTS, s->max_constraints);
-	s->arena_words = env_u64("ABG_SG_ARENA_WORDS", 1, 1ull << 30, s->arena_words);
-	s->max_lanes = (uint32_t)((env_u64("ABG_SG_LANES", 1, 1u << 20, s->max_lanes) + 63) / 64 * 64);
+	s->stream = stream;
+	s->batch = st::env_u64("ABG_SG_BATCH", 1, 1ull << 24, s->batch);
+	s->stack_depth = (uint32_t)st::env_u64("ABG_SG_STACK_DEPTH", 1, 1u << 16, s->stack_depth);
+	s->max_constraints = (uint32_t)st::env_u64("ABG_SG_MAX_CONSTRAINTS", 1, abg::SG_MAX_CONSTRAINTS, s->max_constraints);
+	s->arena_words = st::env_u64("ABG_SG_ARENA_WORDS", 1, 1ull << 30, s->arena_words);
+	s->max_lanes = (uint32_t)((st::env_u64("ABG_SG_LANES", 1, 1u << 20, s->max_lanes) + 63) / 64 * 64);
 	*out = s;
 	return ABG_OK;
 }
@@ -268,7 +222,7 @@ int abg_sg_set_graph(abg_sg* s, uint64_t nv, const uint64_t* edge_offsets, const
 	if (e == hipSuccess) e = upload(&s->d_etgt, s->etgt, s->stream);
 	if (e == hipSuccess) e = upload(&s->d_edist, s->edist, s->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-	if (e != hipSuccess) { s->free_graph(); return sg_fail(s, e, "uploading the graph"); }
+	if (e != hipSuccess) { s->free_graph(); return st::fail(s->error, e, "uploading the graph"); }
 	s->have_graph = true;
 	return ABG_OK;
 }
@@ -319,10 +273,10 @@ int abg_sg_search(abg_sg* s, uint64_t nsearch, const uint32_t* origins, const ui
 	(void)hipSetDevice(s->device);
 	hipError_t e = hipSuccess;
 	if (!device.empty()) {
-		e = grow(&s->din, &s->in_cap, std::max<size_t>(ncall, 1) * 8 + 64);
+		e = st::grow(&s->din, &s->in_cap, std::max<size_t>(ncall, 1) * 8 + 64);
 		if (e == hipSuccess) e = hipMemcpyAsync(s->din, cv.data(), ncall * 4, hipMemcpyHostToDevice, s->stream);
 		if (e == hipSuccess) e = hipMemcpyAsync((uint32_t*)s->din + ncall, cb.data(), ncall * 4, hipMemcpyHostToDevice, s->stream);
-		if (e != hipSuccess) return sg_fail(s, e, "copying the constraints to the device");
+		if (e != hipSuccess) return st::fail(s->error, e, "copying the constraints to the device");
 	}
 	const abg::SGGraph dg{ s->d_voff, s->d_vlen, s->d_etgt, s->d_edist, nv };
 	// per search the arena records of its paths, in discovery order: (offset into the batch's arena copy, length)
@@ -347,10 +301,10 @@ int abg_sg_search(abg_sg* s, uint64_t nsearch, const uint32_t* origins, const ui
 		const uint32_t lanes = (uint32_t)std::min<uint64_t>((nb + 63) / 64 * 64, s->max_lanes);
 		// jobs, then the three counters and the arena cursor, then visited and status
 		const size_t jobs_bytes = (nb * sizeof(abg::SGJob) + 63) & ~(size_t)63;
-		e = grow(&s->dout, &s->out_cap, jobs_bytes + 64 + nb * 8);
-		if (e == hipSuccess) e = grow(&s->dstack, &s->stack_cap, (size_t)lanes * s->stack_depth * sizeof(uint4));
-		if (e == hipSuccess) e = grow(&s->darena, &s->arena_cap, (size_t)s->arena_words * 4);
-		if (e != hipSuccess) { rc = sg_fail(s, e, "allocating a batch"); break; }
+		e = st::grow(&s->dout, &s->out_cap, jobs_bytes + 64 + nb * 8);
+		if (e == hipSuccess) e = st::grow(&s->dstack, &s->stack_cap, (size_t)lanes * s->stack_depth * sizeof(uint4));
+		if (e == hipSuccess) e = st::grow(&s->darena, &s->arena_cap, (size_t)s->arena_words * 4);
+		if (e != hipSuccess) { rc = st::fail(s->error, e, "allocating a batch"); break; }
 		char* base = (char*)s->dout;
 		unsigned long long* dcounters = (unsigned long long*)(base + jobs_bytes);
 		uint32_t* dvis = (uint32_t*)(base + jobs_bytes + 64);
@@ -358,31 +312,29 @@ int abg_sg_search(abg_sg* s, uint64_t nsearch, const uint32_t* origins, const ui
 		e = hipMemcpyAsync(base, jobs.data(), nb * sizeof(abg::SGJob), hipMemcpyHostToDevice, s->stream);
 		const unsigned long long zero[8] = { 0, 0, 0, 0, ~0ull, 0, 0, 0 }; // [3] the arena cursor, [4] where its records end
 		if (e == hipSuccess) e = hipMemcpyAsync(dcounters, zero, 64, hipMemcpyHostToDevice, s->stream);
-		if (e != hipSuccess) { rc = sg_fail(s, e, "copying a batch to the device"); break; }
+		if (e != hipSuccess) { rc = st::fail(s->error, e, "copying a batch to the device"); break; }
 		{
-			hipEvent_t t0 = nullptr, t1 = nullptr;
-			if (s->profiling) { (void)hipEventCreate(&t0); (void)hipEventCreate(&t1); (void)hipEventRecord(t0, s->stream); }
+			st::Timed t(s->prof, s->stream, "sg_search", s->profiling != 0);
 			hipLaunchKernelGGL(sg_search_kernel, dim3(lanes / 64), dim3(64), 0, s->stream, dg, (const abg::SGJob*)base, (const uint32_t*)s->din,
 			    (const int32_t*)((uint32_t*)s->din + ncall), (uint32_t)nb, max_cost, max_paths, (uint4*)s->dstack, s->stack_depth, (uint32_t*)s->darena,
 			    (uint64_t)s->arena_words, dcounters + 3, dcounters, dvis, dstat, s->profiling == 2 ? 1 : 0);
 			e = hipGetLastError();
-			if (s->profiling) { (void)hipEventRecord(t1, s->stream); s->pending.push_back({ "sg_search", { t0, t1 } }); }
 		}
-		if (e != hipSuccess) { rc = sg_fail(s, e, "launching the search"); break; }
+		if (e != hipSuccess) { rc = st::fail(s->error, e, "launching the search"); break; }
 		unsigned long long hc[5] = { 0, 0, 0, 0, 0 };
 		hvis.resize(nb); hstat.resize(nb);
 		e = hipMemcpyAsync(hc, dcounters, 40, hipMemcpyDeviceToHost, s->stream);
 		if (e == hipSuccess) e = hipMemcpyAsync(hvis.data(), dvis, nb * 4, hipMemcpyDeviceToHost, s->stream);
 		if (e == hipSuccess) e = hipMemcpyAsync(hstat.data(), dstat, nb * 4, hipMemcpyDeviceToHost, s->stream);
 		if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-		if (e != hipSuccess) { rc = sg_fail(s, e, "the search"); break; }
+		if (e != hipSuccess) { rc = st::fail(s->error, e, "the search"); break; }
 		s->thin_steps += hc[1];
 		s->all_steps += hc[2];
 		const uint64_t used = std::min<uint64_t>(std::min<uint64_t>(hc[3], hc[4]), s->arena_words);
 		harena.resize(used);
 		if (used) {
 			e = hipMemcpy(harena.data(), s->darena, used * 4, hipMemcpyDeviceToHost);
-			if (e != hipSuccess) { rc = sg_fail(s, e, "copying the paths back"); break; }
+			if (e != hipSuccess) { rc = st::fail(s->error, e, "copying the paths back"); break; }
 		}
 		again.clear();
 		for (uint64_t i = 0; i < nb; ++i) {
@@ -449,16 +401,12 @@ int abg_sg_profile_get(abg_sg* s, const char* name, double* total_ms, uint64_t* 
 {
 	if (!s || !name) return ABG_EINVAL;
 	(void)hipSetDevice(s->device);
-	prof_drain(s);
 	if (total_ms) *total_ms = 0;
 	// not kernels: wave steps of the profiled calls, those taken with fewer than half the lanes busy, and searches redone on the host
 	if (!strcmp(name, "sg_steps")) { if (launches) *launches = s->all_steps; return ABG_OK; }
 	if (!strcmp(name, "sg_thin_steps")) { if (launches) *launches = s->thin_steps; return ABG_OK; }
 	if (!strcmp(name, "sg_redone")) { if (launches) *launches = s->redone; return ABG_OK; }
-	auto it = s->prof.find(name);
-	if (total_ms) *total_ms = it == s->prof.end() ? 0 : it->second.ms;
-	if (launches) *launches = it == s->prof.end() ? 0 : it->second.launches;
-	return ABG_OK;
+	return s->prof.get(name, total_ms, launches);
 }
 
 } // extern "C"

@@ -85,3 +85,20 @@ def test_rresolver_has_no_cpu_fallback(tmp_path):
     r = subprocess.run([os.path.join(build.BIN_DIR, "abyss-rresolver-short"), "-b8M", "-k32", "-c", "o.fa", "-g", "o.dot", "--dot", "rr_k32-1.fa", "rr_k32-1.dot"] + reads,
                        cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
     assert r.returncode == 1 and b"no HIP device" in r.stderr and not os.path.exists(tmp_path / "o.fa")
+
+
+# every handle class but BloomDBG, with the smallest valid arguments: each goes through its own abg_XX_create
+HANDLES = [
+    (api.OverlapJoin, (), "abg_overlap"), (api.ReadFilter, (1 << 20, 64), "abg_rr"), (api.KonnectorBloom, (32, 1 << 20), "abg_kn"),
+    (api.FMIndex, (), "abg_fm"), (api.DistanceMLE, (), "abg_de"), (api.ContigOverlap, (), "abg_ov"), (api.PathSearch, (), "abg_sg"),
+    (api.PathMerge, (), "abg_mc"), (api.BubbleAlign, (), "abg_pb"), (api.PairMerge, (), "abg_mp"),
+]
+
+
+@pytest.mark.skipif(_have_gpu(), reason="a GPU is present")
+@pytest.mark.parametrize("cls,args,prefix", HANDLES, ids=[h[2] for h in HANDLES])
+def test_no_stage_has_a_cpu_fallback(cls, args, prefix):
+    with pytest.raises(api.AbyssAmdError) as e:
+        cls(*args)
+    assert "%s_create failed (%d)" % (prefix, _lib.ABG_ENODEV) in str(e.value)
+    assert "no HIP device available (abyss_amd has no CPU fallback)" in str(e.value)
