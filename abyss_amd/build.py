@@ -49,6 +49,11 @@ def csrc_files():
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [os.path.join(ROOT, "include", "abyss_amd.h")]
 
 
+def host_files():
+    host = os.path.join(CSRC, "host")
+    return [os.path.join(host, f) for f in sorted(os.listdir(host))]
+
+
 OBJ_DIR = os.path.join(ROOT, "abyss_amd", "lib", "obj")
 # translation units of the library and what each is rebuilt for (the big one takes minutes; the others seconds)
 UNITS = {
@@ -113,8 +118,7 @@ def build_cli(force: bool = False) -> str:
     out = os.path.join(BIN_DIR, CLI[0][0])
     if not os.path.exists(os.path.join(host, CLI[0][1])):
         return ""
-    deps = [os.path.join(host, f) for f in os.listdir(host)]
-    if force or _newer(out, deps + [LIB]):
+    if force or _newer(out, host_files() + [LIB]):
         os.makedirs(BIN_DIR, exist_ok=True)
         build_lib()
         for name, main, extra in CLI:
@@ -134,28 +138,22 @@ def build_oracle(force: bool = False) -> None:
 
 
 HOSTCHECK_DIR = os.path.join(ROOT, "tests", "hostcheck")
-_GRAPH_HOST = ["rresolver_core.h", "graph_writers.h", "fasta_reader.h", "si_bytes.h"]
-# the stand-alone checkers: (constant, source under tests/hostcheck, what else it is rebuilt for under csrc, flags between -O2 and -o,
-# flags after the source)
+# the stand-alone checkers: (constant, source under tests/hostcheck, the device headers under csrc it is rebuilt for, flags between -O2
+# and -o, flags after the source).  Each of them includes something under csrc/host and is rebuilt for any file there, as the
+# binaries are: a header one of those includes need not be listed anywhere.
 CHECKERS = [
-    ("READER_CHECK", "reader_check.cc", ["host/fasta_reader.h"], [], []),
-    ("ADJLIST_CHECK", "adjlist_check.cc", ["host/adjlist_core.h", "host/fasta_reader.h"], [],
-     ["-L" + HOSTCHECK_DIR, "-lhostcheck", "-Wl,-rpath,$ORIGIN"]),
-    ("RRESOLVER_CHECK", "rresolver_check.cc", ["abg_rr.h", "abg_core.h"] + ["host/" + f for f in _GRAPH_HOST], ["-Wno-unknown-pragmas"], ["-lpthread"]),
-    ("KN_CHECK", "kn_check.cc", ["abg_kn.h", "abg_core.h", "host/bloom_core.h", "host/fasta_reader.h"], ["-Wno-unknown-pragmas"], ["-lpthread"]),
-    ("FM_CHECK", "fm_check.cc", ["abg_fm.h", "abg_core.h", "host/map_core.h", "host/fasta_reader.h"], ["-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("READER_CHECK", "reader_check.cc", [], [], []),
+    ("ADJLIST_CHECK", "adjlist_check.cc", [], [], ["-L" + HOSTCHECK_DIR, "-lhostcheck", "-Wl,-rpath,$ORIGIN"]),
+    ("RRESOLVER_CHECK", "rresolver_check.cc", ["abg_rr.h", "abg_core.h"], ["-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("KN_CHECK", "kn_check.cc", ["abg_kn.h", "abg_core.h"], ["-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("FM_CHECK", "fm_check.cc", ["abg_fm.h", "abg_core.h"], ["-Wno-unknown-pragmas"], ["-lpthread"]),
     # (no -march and no contraction: its sums are the reference's, bit for bit)
-    ("DE_CHECK", "de_check.cc", ["abg_de.h", "abg_core.h", "host/distanceest_core.h"], ["-ffp-contract=off", "-Wno-unknown-pragmas"], ["-lpthread"]),
-    ("OV_CHECK", "ov_check.cc", ["abg_ov.h", "abg_core.h", "host/overlap_core.h"] + ["host/" + f for f in _GRAPH_HOST],
-     ["-Wno-unknown-pragmas"], ["-lpthread"]),
-    ("SG_CHECK", "sg_check.cc", ["abg_sg.h", "abg_core.h", "host/simplegraph_core.h", "host/overlap_core.h"] + ["host/" + f for f in _GRAPH_HOST],
-     ["-Wno-unknown-pragmas"], ["-lpthread"]),
-    ("MC_CHECK", "mc_check.cc", ["abg_mc.h", "abg_ov.h", "abg_core.h", "host/mergecontigs_core.h", "host/overlap_core.h"] + ["host/" + f for f in _GRAPH_HOST],
-     ["-Wno-unknown-pragmas"], ["-lpthread"]),
-    ("PB_CHECK", "pb_check.cc", ["abg_pb.h", "abg_mc.h", "abg_ov.h", "abg_core.h", "host/popbubbles_core.h"] + ["host/" + f for f in _GRAPH_HOST],
-     ["-Wno-unknown-pragmas"], ["-lpthread"]),
-    ("MP_CHECK", "mp_check.cc", ["abg_mp.h", "abg_mc.h", "abg_ov.h", "abg_core.h", "host/mergepairs_core.h", "host/fasta_reader.h"],
-     ["-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("DE_CHECK", "de_check.cc", ["abg_de.h", "abg_core.h"], ["-ffp-contract=off", "-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("OV_CHECK", "ov_check.cc", ["abg_ov.h", "abg_core.h"], ["-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("SG_CHECK", "sg_check.cc", ["abg_sg.h", "abg_core.h"], ["-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("MC_CHECK", "mc_check.cc", ["abg_mc.h", "abg_ov.h", "abg_core.h"], ["-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("PB_CHECK", "pb_check.cc", ["abg_pb.h", "abg_mc.h", "abg_ov.h", "abg_core.h"], ["-Wno-unknown-pragmas"], ["-lpthread"]),
+    ("MP_CHECK", "mp_check.cc", ["abg_mp.h", "abg_mc.h", "abg_ov.h", "abg_core.h"], ["-Wno-unknown-pragmas"], ["-lpthread"]),
 ]
 for _name, _src, _deps, _flags, _libs in CHECKERS:  # READER_CHECK = .../tests/hostcheck/reader_check, and so on
     globals()[_name] = os.path.join(HOSTCHECK_DIR, _src[:-len(".cc")])
@@ -169,7 +167,7 @@ def build_hostcheck(force: bool = False) -> str:
     for name, source, deps, flags, libs in CHECKERS:
         out, src = globals()[name], os.path.join(HOSTCHECK_DIR, source)
         # (adjlist_check links libhostcheck.so, so it is rebuilt after it)
-        if force or _newer(out, [src] + [os.path.join(CSRC, d) for d in deps] + ([HOSTCHECK] if "-lhostcheck" in libs else [])):
+        if force or _newer(out, [src] + [os.path.join(CSRC, d) for d in deps] + host_files() + ([HOSTCHECK] if "-lhostcheck" in libs else [])):
             _run(["g++", "-std=c++17", "-O2"] + flags + ["-o", out, src] + libs)
     return HOSTCHECK
 

@@ -17,6 +17,7 @@
 
 #include "fasta_reader.h"
 #include "graph_writers.h"
+#include "host_cli.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -121,11 +122,7 @@ static const char USAGE_MESSAGE[] =
 // AdjList.cpp:323-378.  Returns false when the caller should exit with `*status`.
 inline bool parse_options(int argc, char** argv, Options& o, int* device, int* status)
 {
-	{
-		std::ostringstream ss;
-		for (int i = 0; i < argc; i++) ss << (i ? " " : "") << argv[i];
-		o.commandLine = ss.str();
-	}
+	o.commandLine = cli::command_line(argc, argv);
 	enum { OPT_HELP = 1, OPT_VERSION, OPT_DB, OPT_LIBRARY, OPT_STRAIN, OPT_SPECIES, OPT_GPU };
 	static int format = ADJ, ss = 0;
 	static const struct option longopts[] = {
@@ -160,8 +157,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* device, int* s
 		case OPT_GPU: arg >> *device; break;
 		}
 		if (optarg != NULL && !arg.eof()) {
-			fprintf(stderr, ABG_ADJ_PROGRAM ": invalid option: `-%c%s'\n", (char)c, optarg);
-			*status = EXIT_FAILURE;
+			*status = cli::invalid_option(ABG_ADJ_PROGRAM, c, optarg);
 			return false;
 		}
 	}
@@ -172,7 +168,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* device, int* s
 	if (!die && o.k < 2) { fprintf(stderr, ABG_ADJ_PROGRAM ": -k must be at least 2\n"); die = true; }
 	if (!die && o.k - 1 > 256) { fprintf(stderr, ABG_ADJ_PROGRAM ": -k must be at most 257\n"); die = true; }
 	if (die) {
-		fprintf(stderr, "Try `" ABG_ADJ_PROGRAM " --help' for more information.\n");
+		cli::try_help(ABG_ADJ_PROGRAM);
 		*status = EXIT_FAILURE;
 		return false;
 	}

@@ -7,6 +7,7 @@
 // abyss-index --bwt2fm and -d/--decompress.  abyss-pe passes none of them.
 #pragma once
 #include "fasta_reader.h"
+#include "host_cli.h"
 
 #include <getopt.h>
 
@@ -246,7 +247,7 @@ struct MapOptions {
 // false: leave with *status (help, version, or an error already reported)
 inline bool parse_map_options(int argc, char** argv, MapOptions& o, int* status)
 {
-	for (int i = 0; i < argc; i++) { if (i) o.commandLine += ' '; o.commandLine += argv[i]; }
+	o.commandLine = cli::command_line(argc, argv);
 	enum { OPT_HELP = 1, OPT_VERSION, OPT_ALPHA, OPT_DNA, OPT_PROTEIN, OPT_DB, OPT_LIBRARY, OPT_STRAIN, OPT_SPECIES };
 	const struct option longopts[] = {
 		{ "append-comment", no_argument, NULL, 'C' }, { "sample", required_argument, NULL, 's' },
@@ -290,8 +291,7 @@ inline bool parse_map_options(int argc, char** argv, MapOptions& o, int* status)
 		}
 		}
 		if (optarg != NULL && !arg.eof()) {
-			fprintf(stderr, ABG_MAP_PROGRAM ": invalid option: `-%c%s'\n", (char)c, optarg);
-			*status = EXIT_FAILURE;
+			*status = cli::invalid_option(ABG_MAP_PROGRAM, c, optarg);
 			return false;
 		}
 	}
@@ -309,7 +309,7 @@ inline bool parse_map_options(int argc, char** argv, MapOptions& o, int* status)
 		die = true;
 	}
 	if (die) {
-		fprintf(stderr, "Try `" ABG_MAP_PROGRAM " --help' for more information.\n");
+		cli::try_help(ABG_MAP_PROGRAM);
 		return false;
 	}
 	o.target = argv[argc - 1];
@@ -646,10 +646,7 @@ inline int index_main(int argc, char** argv, const MakeBackend& make)
 		case OPT_HELP: fputs(INDEX_USAGE, stdout); return EXIT_SUCCESS;
 		case OPT_VERSION: fputs(ABG_INDEX_PROGRAM " (ABySS, abyss_amd) " ABG_IO_VERSION "\n", stdout); return EXIT_SUCCESS;
 		}
-		if (optarg != NULL && !arg.eof()) {
-			fprintf(stderr, ABG_INDEX_PROGRAM ": invalid option: `-%c%s'\n", (char)c, optarg);
-			return EXIT_FAILURE;
-		}
+		if (optarg != NULL && !arg.eof()) return cli::invalid_option(ABG_INDEX_PROGRAM, c, optarg);
 	}
 	if (bwt2fm) refused = "--bwt2fm";
 	if (refused) {
@@ -659,7 +656,7 @@ inline int index_main(int argc, char** argv, const MakeBackend& make)
 	if (argc - optind < 1) { fprintf(stderr, ABG_INDEX_PROGRAM ": missing arguments\n"); die = true; }
 	if (argc - optind > 1) { fprintf(stderr, ABG_INDEX_PROGRAM ": too many arguments\n"); die = true; }
 	if (die) {
-		fprintf(stderr, "Try `" ABG_INDEX_PROGRAM " --help' for more information.\n");
+		cli::try_help(ABG_INDEX_PROGRAM);
 		return EXIT_FAILURE;
 	}
 	if (sampleSA == 0) { fprintf(stderr, ABG_INDEX_PROGRAM ": -s must be at least 1\n"); return EXIT_FAILURE; }

@@ -20,11 +20,15 @@
 // Where the reference aborts or trips an assert, this prints an error naming the input and exits 1: a path edge the graph lacks
 // (after the reference's own `error: no edge` line), an edge of distance >= 0 on a path, a FASTA file whose order differs from the
 // graph's, an empty FASTA file, colour-space contigs, a malformed node name.  The graph is read in the ADJ and GraphViz formats
-// (rresolver_core.h's readers); the others are refused.  --db, --library, --strain and --species are accepted and ignored.
+// (contig_graph.h's readers); the others are refused.  --db, --library, --strain and --species are accepted and ignored.
 #pragma once
 
-#include "overlap_core.h"
+#include "contig_graph.h"
+#include "fasta_reader.h"
+#include "host_cli.h"
 
+#include <cmath>
+#include <getopt.h>
 #include <iomanip>
 #include <iostream>
 #include <limits>
@@ -33,7 +37,7 @@ namespace mc {
 
 #define ABG_MC_PROGRAM "MergeContigs"
 
-using abgrr::V;
+using cg::V; using cg::Node; using cg::Path; using cg::show_float;
 using abgio::ADJ; using abgio::DOT; using abgio::GFA1; using abgio::GFA2; using abgio::SAM;
 enum { DOT_MEANCOV = 100 };
 
@@ -83,9 +87,6 @@ struct Options { // namespace opt, MergeContigs.cpp:78-101
 	std::string out = "-", graphPath, commandLine, contigPath, adjPath, pathPath;
 };
 
-typedef int32_t Node; // ContigNode: a vertex, or -n for the gap of n bases (ContigNode.h:41-48)
-typedef std::vector<Node> Path;
-
 // What the host asks of the merge: path i is nodes[noff[i] .. noff[i + 1]], ov[j] the overlap of nodes[j] with what precedes it.
 // Back come the sequences, seqs[soff[i] .. soff[i + 1]], their ACGT counts, and the stderr text of the paths merged the slow way,
 // logs[loff[i] .. loff[i + 1]], with the placeholders of abg_mc.h for names.
@@ -100,11 +101,7 @@ struct Merger {
 // main's option loop, MergeContigs.cpp:437-519.  Returns false when the caller should exit with `*status`.
 inline bool parse_options(int argc, char** argv, Options& o, int* status)
 {
-	{
-		std::ostringstream ss;
-		for (int i = 0; i < argc; i++) ss << (i ? " " : "") << argv[i];
-		o.commandLine = ss.str();
-	}
+	o.commandLine = cli::command_line(argc, argv);
 	enum { OPT_HELP = 1, OPT_VERSION, OPT_DB, OPT_LIBRARY, OPT_STRAIN, OPT_SPECIES };
 	static int format = DOT, onlyMerged = 0;
 	static const struct option longopts[] = {
@@ -133,8 +130,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 		case OPT_DB: case OPT_LIBRARY: case OPT_STRAIN: case OPT_SPECIES: arg >> ignored; break; // (this build keeps no database)
 		} // (--path is in the reference's table and in no case of its switch: its argument is never read, so it is never at its end)
 		if (optarg != NULL && !arg.eof()) {
-			fprintf(stderr, ABG_MC_PROGRAM ": invalid option: `-%c%s'\n", (char)c, optarg);
-			*status = EXIT_FAILURE;
+			*status = cli::invalid_option(ABG_MC_PROGRAM, c, optarg);
 			return false;
 		}
 	}
@@ -144,7 +140,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 	if (argc - optind < 2) { fprintf(stderr, ABG_MC_PROGRAM ": missing arguments\n"); die = true; }
 	if (argc - optind > 3) { fprintf(stderr, ABG_MC_PROGRAM ": too many arguments\n"); die = true; }
 	if (die) {
-		fprintf(stderr, "Try `" ABG_MC_PROGRAM " --help' for more information.\n");
+		cli::try_help(ABG_MC_PROGRAM);
 		*status = EXIT_FAILURE;
 		return false;
 	}
@@ -154,21 +150,9 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 	return true;
 }
 
-[[noreturn]] inline void fail(const std::string& msg)
-{
-	fflush(stdout);
-	fprintf(stderr, ABG_MC_PROGRAM ": error: %s\n", msg.c_str());
-	exit(EXIT_FAILURE);
-}
+[[noreturn]] inline void fail(const std::string& msg) { cli::fail(ABG_MC_PROGRAM, msg); }
 
 inline bool is_acgt(char c) { return strchr("ACGTacgt", c) != nullptr && c != 0; } // isACGT, Sequence.h:21-25
-
-inline std::string show_float(float x, int precision = 6) // operator<<(ostream&, float)
-{
-	char b[64];
-	snprintf(b, sizeof b, "%.*g", precision, (double)x);
-	return b;
-}
 
 // Histogram (Common/Histogram.h) as far as printContiguityStats reads it
 struct LengthHistogram {
@@ -231,36 +215,14 @@ class Run {
 	Run(Options& o, Merger& m) : opt(o), merger(m) {}
 	Options& opt;
 	Merger& merger;
-	abgrr::Graph graph;
+	cg::Graph graph;
 	std::vector<Contig> contigs;
 	std::vector<std::string> pathIDs;
 	std::vector<Path> paths;
 	int precision = 6; // of the floats written to stderr
 
-	std::string name(Node u) const { return u < 0 ? std::to_string(-(int64_t)u) + "N" : graph.vname((V)u); }
-	std::string show(const Path& p) const // operator<<(ostream&, const ContigPath&), ContigPath.h:37-45
-	{
-		std::string s;
-		for (size_t i = 0; i < p.size(); ++i) { if (i) s += ' '; s += name(p[i]); }
-		return s;
-	}
-
-	void read_graph()
-	{
-		const std::string text = abgrr::slurp(opt.adjPath);
-		size_t p = 0;
-		while (p < text.size() && isspace((unsigned char)text[p])) p++;
-		const int c = p < text.size() ? text[p] : EOF;
-		abgrr::Options ro;
-		ro.k = opt.k;
-		graph.k = opt.k;
-		if (c == 'd') abgrr::read_dot(text, graph, ro);
-		else if (c == '@' || c == 'H' || c == '>' || c == 'g')
-			fail("`" + opt.adjPath + "': this build reads the contig graph in GraphViz (--dot) or ADJ format only");
-		else abgrr::read_adj(text, graph, ro);
-		graph.k = opt.k;
-		if (graph.nv() & 1) fail("`" + opt.adjPath + "': a contig is missing one of its two vertices");
-	}
+	std::string name(Node u) const { return cg::node_name(graph, u); }
+	std::string show(const Path& p) const { return cg::show_path(graph, p); }
 
 	void read_contigs()
 	{
@@ -330,7 +292,7 @@ class Run {
 			return std::string(opt.k - 1, 'N') + std::string(n, n < opt.k ? 'n' : 'N');
 		}
 		const std::string& s = contigs[(size_t)u >> 1].seq;
-		return (u & 1) ? abgrr::reverse_complement(s) : s;
+		return (u & 1) ? cg::reverse_complement(s) : s;
 	}
 
 	// get(vertex_bundle, g, u), MergeContigs.cpp:206-210
@@ -340,22 +302,6 @@ class Run {
 		else { l = graph.length[u]; c = graph.coverage[u]; }
 	}
 	int distance(Node u, Node v) const { return (u < 0 || v < 0) ? -(int)opt.k + 1 : graph.find_edge((V)u, (V)v)->d; }
-
-	// copy_out_edges, ContigGraphAlgorithms.h:54-87
-	void copy_out_edges(V u, V uout)
-	{
-		const std::vector<abgrr::Edge> edges = graph.adj[u];
-		bool palindrome = false;
-		int palindrome_d = 0;
-		for (const abgrr::Edge& e : edges) {
-			if ((e.v ^ 1) == u) { palindrome = true; palindrome_d = e.d; }
-			else graph.add_edge(uout, e.v, e.d);
-		}
-		if (palindrome) {
-			graph.add_edge(uout, u ^ 1, palindrome_d);
-			graph.add_edge(uout, uout ^ 1, palindrome_d);
-		}
-	}
 
 	// outputGraph, MergeContigs.cpp:388-432
 	void output_graph()
@@ -374,8 +320,8 @@ class Run {
 			}
 			if (path.front() < 0 || path.back() < 0) fail("path `" + pathIDs[i] + "' begins or ends with a gap, which has no place in the graph");
 			const V u = graph.add_vertex(l, c);
-			copy_out_edges((V)path.front() ^ 1, u ^ 1); // copy_in_edges
-			copy_out_edges((V)path.back(), u);
+			cg::copy_out_edges(graph, (V)path.front() ^ 1, u ^ 1); // copy_in_edges
+			cg::copy_out_edges(graph, (V)path.back(), u);
 			graph.put_name(u, pathIDs[i]);
 		}
 		for (size_t i = 0; i < paths.size(); ++i) {
@@ -395,7 +341,7 @@ class Run {
 			else abgio::write_graph(o, graph, opt.format, ABG_MC_PROGRAM, opt.commandLine);
 		}
 		if (fclose(g) != 0) { fflush(stdout); fprintf(stderr, "error: `%s': %s\n", opt.graphPath.c_str(), strerror(errno)); exit(EXIT_FAILURE); }
-		if (opt.verbose > 0) { abgrr::print_graph_stats(stderr, graph); precision = 2; } // (printGraphStats leaves cerr at setprecision(2), GraphUtil.h:56-63)
+		if (opt.verbose > 0) { cg::print_graph_stats(stderr, graph); precision = 2; } // (printGraphStats leaves cerr at setprecision(2), GraphUtil.h:56-63)
 	}
 	// dot_writer with the vertex property as opt::format == DOT_MEANCOV prints it (ContigProperties.h:86-99)
 	void write_dot_meancov(abgio::Out& out) const
@@ -421,7 +367,7 @@ class Run {
 	{
 		if (!opt.adjPath.empty()) {
 			if (opt.verbose > 0) fprintf(stderr, "Reading `%s'...\n", opt.adjPath.c_str());
-			read_graph();
+			cg::load_graph(opt.adjPath, opt.k, graph, fail);
 			if (opt.verbose > 0) fprintf(stderr, "Read %llu vertices.\n", (unsigned long long)graph.nv());
 		}
 		graph.k = opt.k;
@@ -474,7 +420,7 @@ class Run {
 				if (j > 0) {
 					int d = -(int)opt.k + 1;
 					if (p[j - 1] >= 0 && p[j] >= 0) {
-						const abgrr::Edge* e = graph.find_edge((V)p[j - 1], (V)p[j]);
+						const cg::Edge* e = graph.find_edge((V)p[j - 1], (V)p[j]);
 						if (!e) {
 							stop = i;
 							stop_line = "error: no edge " + name(p[j - 1]) + " -> " + name(p[j]) + "\n";
@@ -505,11 +451,8 @@ class Run {
 			std::string err;
 			if (!merger.open(err)) fail(err);
 			std::string bytes;
-			std::vector<uint64_t> offsets{ 0 };
-			size_t total = 0;
-			for (const Contig& c : contigs) total += c.seq.size();
-			bytes.reserve(total);
-			for (const Contig& c : contigs) { bytes += c.seq; offsets.push_back(bytes.size()); }
+			std::vector<uint64_t> offsets;
+			cg::flatten(contigs, [](const Contig& c) -> const std::string& { return c.seq; }, bytes, offsets);
 			if (!merger.set_contigs(bytes, offsets, err)) fail(err);
 			if (!merger.merge(opt.k, noff, nodes, ov, opt.verbose, soff, seqs, acgt, loff, logs, err)) fail(err);
 		}

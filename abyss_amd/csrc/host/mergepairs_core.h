@@ -12,6 +12,7 @@
 #pragma once
 #include "../abg_mp.h"
 #include "fasta_reader.h"
+#include "host_cli.h"
 
 #include <getopt.h>
 
@@ -133,8 +134,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 		case OPT_VERSION: fputs(VERSION_MESSAGE, stdout); *status = EXIT_SUCCESS; return false;
 		}
 		if (optarg != NULL && !arg.eof()) {
-			fprintf(stderr, ABG_MP_PROGRAM ": invalid option: `-%c%s'\n", (char)c, optarg);
-			*status = EXIT_FAILURE;
+			*status = cli::invalid_option(ABG_MP_PROGRAM, c, optarg);
 			return false;
 		}
 	}
@@ -145,7 +145,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 	if (argc - optind < 2) { fprintf(stderr, ABG_MP_PROGRAM ": missing arguments\n"); die = true; }
 	if (argc - optind > 2) { fprintf(stderr, ABG_MP_PROGRAM ": too many arguments\n"); die = true; }
 	if (die) {
-		fprintf(stderr, "Try `" ABG_MP_PROGRAM " --help' for more information.\n");
+		cli::try_help(ABG_MP_PROGRAM);
 		*status = EXIT_FAILURE;
 		return false;
 	}

@@ -26,19 +26,22 @@
 // Where the reference trips an assert, this prints an error naming the input and exits 1: an empty FASTA file, a distance of
 // 100000 or more on a scaffolded edge, an estimate between a vertex and itself or its complement in a dot scaffold graph, a
 // contig named by the graph that the FASTA file lacks, a contig shorter than k - 1 at a scaffolded end.  Colour-space contigs are
-// refused.  The adjacency graph is read in the ADJ and GraphViz formats (rresolver_core.h's readers).
+// refused.  The adjacency graph is read in the ADJ and GraphViz formats (contig_graph.h's readers).
 #pragma once
 
-#include "rresolver_core.h"
+#include "contig_graph.h"
+#include "fasta_reader.h"
+#include "host_cli.h"
 
 #include <climits>
 #include <cmath>
+#include <getopt.h>
 
 namespace ov {
 
 #define ABG_OV_PROGRAM "Overlap"
 
-using abgrr::V;
+using cg::V;
 using abgio::ADJ; using abgio::ASQG; using abgio::DOT; using abgio::GFA1; using abgio::GFA2; using abgio::SAM;
 
 static const char VERSION_MESSAGE[] =
@@ -98,11 +101,7 @@ struct Searcher {
 // main's option loop, Overlap.cpp:376-425.  Returns false when the caller should exit with `*status`.
 inline bool parse_options(int argc, char** argv, Options& o, int* status)
 {
-	{
-		std::ostringstream ss;
-		for (int i = 0; i < argc; i++) ss << (i ? " " : "") << argv[i];
-		o.commandLine = ss.str();
-	}
+	o.commandLine = cli::command_line(argc, argv);
 	enum { OPT_HELP = 1, OPT_VERSION };
 	static int scaffold = 1, mask = 1, ss = 0, format = ADJ;
 	static const struct option longopts[] = {
@@ -132,8 +131,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 		case OPT_VERSION: fputs(VERSION_MESSAGE, stdout); *status = EXIT_SUCCESS; return false;
 		}
 		if (optarg != NULL && !arg.eof()) {
-			fprintf(stderr, ABG_OV_PROGRAM ": invalid option: `-%c%s'\n", (char)c, optarg);
-			*status = EXIT_FAILURE;
+			*status = cli::invalid_option(ABG_OV_PROGRAM, c, optarg);
 			return false;
 		}
 	}
@@ -143,7 +141,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 	if (argc - optind < 3) { fprintf(stderr, ABG_OV_PROGRAM ": missing arguments\n"); die = true; }
 	if (argc - optind > 3) { fprintf(stderr, ABG_OV_PROGRAM ": too many arguments\n"); die = true; }
 	if (die) {
-		fprintf(stderr, "Try `" ABG_OV_PROGRAM " --help' for more information.\n");
+		cli::try_help(ABG_OV_PROGRAM);
 		*status = EXIT_FAILURE;
 		return false;
 	}
@@ -153,12 +151,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 	return true;
 }
 
-[[noreturn]] inline void fail(const std::string& msg)
-{
-	fflush(stdout);
-	fprintf(stderr, ABG_OV_PROGRAM ": error: %s\n", msg.c_str());
-	exit(EXIT_FAILURE);
-}
+[[noreturn]] inline void fail(const std::string& msg) { cli::fail(ABG_OV_PROGRAM, msg); }
 
 // DistanceEst (Estimate.h:26-38) with the two members Overlap adds (Overlap.cpp:212-237)
 struct Est {
@@ -208,7 +201,7 @@ struct DistCall { unsigned ref; bool rc; V pair; Est est; };
 // record(ref) for every record, then estimate(ref, rc, vertex, distance, numPairs, stdDev) for each of its estimates in file order.
 // A name the graph lacks ends the run as Graph::find_contig does; `bad` is given the message for a malformed estimate.
 template <class Record, class Estimate, class Bad>
-inline void read_dist_records(const std::string& text, const abgrr::Graph& graph, const std::string& path, Record record, Estimate estimate, Bad bad)
+inline void read_dist_records(const std::string& text, const cg::Graph& graph, const std::string& path, Record record, Estimate estimate, Bad bad)
 {
 	size_t p = 0;
 	auto skip = [&]() { while (p < text.size() && isspace((unsigned char)text[p])) p++; };
@@ -255,7 +248,7 @@ class Run {
 	Run(Options& o, Searcher& s) : opt(o), searcher(s), scaffoldGraph(0) {}
 	Options& opt;
 	Searcher& searcher;
-	abgrr::Graph graph;
+	cg::Graph graph;
 	std::vector<std::string> contigs; // g_contigs
 	SGraph scaffoldGraph;
 	Stats stats;
@@ -277,7 +270,7 @@ class Run {
 	std::string sequence(V u) const
 	{
 		const std::string& s = contigs[u >> 1];
-		return (u & 1) ? abgrr::reverse_complement(s) : s;
+		return (u & 1) ? cg::reverse_complement(s) : s;
 	}
 
 	void read_contigs()
@@ -291,26 +284,13 @@ class Run {
 	}
 	void read_graph()
 	{
-		const std::string text = abgrr::slurp(opt.adjPath);
-		size_t p = 0;
-		while (p < text.size() && isspace((unsigned char)text[p])) p++;
-		const int c = p < text.size() ? text[p] : EOF;
-		abgrr::Options ro;
-		ro.k = opt.k;
-		graph.k = opt.k;
-		if (c == 'd') abgrr::read_dot(text, graph, ro);
-		else if (c == '@' || c == 'H' || c == '>' || c == 'g')
-			fail("`" + opt.adjPath + "': this build reads the contig graph in GraphViz (--dot) or ADJ format only");
-		else abgrr::read_adj(text, graph, ro);
-		opt.k = ro.k;
-		graph.k = opt.k;
-		if (graph.nv() & 1) fail("`" + opt.adjPath + "': a contig is missing one of its two vertices");
+		cg::load_graph(opt.adjPath, opt.k, graph, fail);
 		if (graph.nv() / 2 > contigs.size())
 			fail("`" + opt.adjPath + "' names " + std::to_string(graph.nv() / 2) + " contigs and `" + opt.contigPath + "' holds " + std::to_string(contigs.size()));
 	}
 
 	// operator>>(istream&, DistanceEst&), Estimate.h:71-104, the GraphViz branch
-	void read_dot_est(abgrr::Cursor& in, Est& o)
+	void read_dot_est(cg::Cursor& in, Est& o)
 	{
 		in.expect("d =");
 		o.distance = in.integer("d");
@@ -319,19 +299,19 @@ class Run {
 		if (in.peek() == ',') { in.expect(", e ="); o.stdDev = real(in); in.expect(", n ="); o.numPairs = in.uns("n"); }
 		else { in.expect(" e ="); o.stdDev = real(in); in.expect(" n ="); o.numPairs = in.uns("n"); }
 	}
-	static float real(abgrr::Cursor& in)
+	static float real(cg::Cursor& in)
 	{
 		in.ws();
 		char* end = nullptr;
 		const float x = strtof(in.s.c_str() + in.p, &end);
-		if (end == in.s.c_str() + in.p) abgrr::die("error: expected a number (e)");
+		if (end == in.s.c_str() + in.p) cg::die("error: expected a number (e)");
 		in.p = (size_t)(end - in.s.c_str());
 		return x;
 	}
 	// read_dot (Graph/DotIO.h:159-309) on DirectedGraph<NoProperty, Overlap> with its vertices already there
 	void read_dot_scaffold(const std::string& text)
 	{
-		abgrr::Cursor in(text);
+		cg::Cursor in(text);
 		in.ws();
 		in.expect("digraph");
 		in.ignore('{');
@@ -364,7 +344,7 @@ class Run {
 		}
 		for (std::string uname; in.quoted(uname);) {
 			in.ws();
-			if (in.eof()) abgrr::die("error: unexpected end of the graph file");
+			if (in.eof()) cg::die("error: unexpected end of the graph file");
 			const char c = in.s[in.p++];
 			if (c == ';') (void)graph.find_vertex(uname);
 			else if (c == '[') { (void)graph.find_vertex(uname); in.ignore(']'); }
@@ -398,7 +378,7 @@ class Run {
 		}
 		in.expect("}");
 		in.ws();
-		if (!in.eof()) abgrr::die("error: Expected end-of-file after the graph");
+		if (!in.eof()) cg::die("error: Expected end-of-file after the graph");
 	}
 	// operator<<(ostream&, const Overlap&), Overlap.cpp:232-236
 	static std::string show(const Est& o) { return "d=" + std::to_string(o.overlap > 0 ? -(int)o.overlap : o.distance); }
@@ -512,8 +492,8 @@ class Run {
 		std::string err;
 		if (!searcher.open(err)) fail(err);
 		std::string bytes;
-		std::vector<uint64_t> off{ 0 };
-		for (const std::string& s : contigs) { bytes += s; off.push_back(bytes.size()); }
+		std::vector<uint64_t> off;
+		cg::flatten(contigs, [](const std::string& s) -> const std::string& { return s; }, bytes, off);
 		if (!searcher.set_contigs(bytes, off, err)) fail(err);
 		const bool all = opt.verbose > 0;
 		std::vector<uint32_t> top, ntop, lengths;
@@ -547,7 +527,7 @@ class Run {
 		read_graph();
 		FILE* out = fopen(opt.out.c_str(), "wb");
 		if (!out) { fprintf(stderr, "error: `%s': %s\n", opt.out.c_str(), strerror(errno)); return EXIT_FAILURE; }
-		const std::string text = abgrr::slurp(opt.estPath);
+		const std::string text = cg::slurp(opt.estPath);
 		scaffoldGraph = SGraph(graph.nv());
 		if (!text.empty() && text[0] == 'd') { // in.peek() == 'd', Overlap.cpp:451
 			read_dot_scaffold(text);

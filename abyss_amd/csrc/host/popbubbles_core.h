@@ -12,7 +12,7 @@
 //   Graph/PopBubbles.h:17-122             topologicalSort, isBubble, discoverBubbles
 //   Graph/DepthFirstSearch.h:13-71        the three passes: in-degree 0, not contiguous-in, the rest
 //   Graph/ContigGraphAlgorithms.h:40-253  contiguous_out / in, assemble_if, merge, assemble, assemble_stranded (the first, copy_out_edges
-//                                         and the graph itself are rresolver_core.h's)
+//                                         and the graph itself are contig_graph.h's)
 //   Common/ContigProperties.h:212-233     EdgeWeightMap;  Graph/GraphUtil.h:43-64 printGraphStats, which leaves the stream at two
 //                                         significant digits: every float written to stderr after it shows them
 // How it differs in structure: the reference aligns a bubble's branches when its loop reaches the bubble.  Here every bubble that
@@ -22,8 +22,12 @@
 // Where the reference fails an assertion the drop-in prints a message and exits 1 (INTEGRATION.md section 11 lists the cases).
 #pragma once
 
-#include "rresolver_core.h"
+#include "contig_graph.h"
+#include "fasta_reader.h"
+#include "host_cli.h"
 
+#include <climits>
+#include <getopt.h>
 #include <iomanip>
 #include <iostream>
 #include <set>
@@ -32,8 +36,7 @@ namespace pb {
 
 #define ABG_PB_PROGRAM "PopBubbles"
 
-using abgrr::V;
-using abgrr::Graph;
+using cg::V; using cg::Graph; using cg::show_float;
 using abgio::ADJ; using abgio::ASQG; using abgio::DOT; using abgio::GFA1; using abgio::GFA2; using abgio::SAM;
 
 static const char VERSION_MESSAGE[] =
@@ -100,11 +103,7 @@ struct Aligner {
 // main's option loop, PopBubbles.cpp:546-618.  Returns false when the caller should exit with `*status`.
 inline bool parse_options(int argc, char** argv, Options& o, int* status)
 {
-	{
-		std::ostringstream ss;
-		for (int i = 0; i < argc; i++) ss << (i ? " " : "") << argv[i];
-		o.commandLine = ss.str();
-	}
+	o.commandLine = cli::command_line(argc, argv);
 	enum { OPT_HELP = 1, OPT_VERSION };
 	static int format = ADJ, scaffold = 0, bubbleGraph = 0, ss = 0;
 	static const struct option longopts[] = {
@@ -136,8 +135,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 		case OPT_VERSION: fputs(VERSION_MESSAGE, stdout); *status = EXIT_SUCCESS; return false;
 		}
 		if (optarg != NULL && !arg.eof()) {
-			fprintf(stderr, ABG_PB_PROGRAM ": invalid option: `-%c%s'\n", (char)c, optarg);
-			*status = EXIT_FAILURE;
+			*status = cli::invalid_option(ABG_PB_PROGRAM, c, optarg);
 			return false;
 		}
 	}
@@ -146,7 +144,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 	if (argc - optind < 2) { fprintf(stderr, ABG_PB_PROGRAM ": missing arguments\n"); die = true; }
 	if (argc - optind > 2) { fprintf(stderr, ABG_PB_PROGRAM ": too many arguments\n"); die = true; }
 	if (die) {
-		fprintf(stderr, "Try `" ABG_PB_PROGRAM " --help' for more information.\n");
+		cli::try_help(ABG_PB_PROGRAM);
 		*status = EXIT_FAILURE;
 		return false;
 	}
@@ -155,19 +153,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 	return true;
 }
 
-[[noreturn]] inline void fail(const std::string& msg)
-{
-	fflush(stdout);
-	fprintf(stderr, ABG_PB_PROGRAM ": error: %s\n", msg.c_str());
-	exit(EXIT_FAILURE);
-}
-
-inline std::string show_float(float x, int precision) // operator<<(ostream&, float)
-{
-	char b[64];
-	snprintf(b, sizeof b, "%.*g", precision, (double)x);
-	return b;
-}
+[[noreturn]] inline void fail(const std::string& msg) { cli::fail(ABG_PB_PROGRAM, msg); }
 
 typedef std::vector<V> Bubble;
 
@@ -187,7 +173,7 @@ class Run {
 
 	void graph_stats()
 	{
-		abgrr::print_graph_stats(stderr, g);
+		cg::print_graph_stats(stderr, g);
 		precision = 2;
 		if (g.nv() == g.num_removed()) { // (-c removed every contig: the reference goes on to its histogram of nothing, 0 / 0 four times)
 			volatile unsigned n = 0;
@@ -199,19 +185,7 @@ class Run {
 	void read_graph()
 	{
 		if (opt.verbose > 0) fprintf(stderr, "Reading `%s'...\n", opt.adjPath.c_str());
-		const std::string text = abgrr::slurp(opt.adjPath);
-		size_t p = 0;
-		while (p < text.size() && isspace((unsigned char)text[p])) p++;
-		const int c = p < text.size() ? text[p] : EOF;
-		abgrr::Options ro;
-		ro.k = opt.k;
-		g.k = opt.k;
-		if (c == 'd') abgrr::read_dot(text, g, ro);
-		else if (c == '@' || c == 'H' || c == '>' || c == 'g')
-			fail("`" + opt.adjPath + "': this build reads the contig graph in GraphViz (--dot) or ADJ format only");
-		else abgrr::read_adj(text, g, ro);
-		g.k = opt.k;
-		if (g.nv() & 1) fail("`" + opt.adjPath + "': a contig is missing one of its two vertices");
+		cg::load_graph(opt.adjPath, opt.k, g, fail);
 		if (opt.verbose > 0) graph_stats();
 	}
 
@@ -282,7 +256,7 @@ class Run {
 			}
 		};
 		for (uint64_t u = 0; u < n; u++) if (colour[u] == 0 && g.in_degree((V)u) == 0) visit((V)u);
-		for (uint64_t u = 0; u < n; u++) if (colour[u] == 0 && !abgrr::Resolver::contiguous_in(g, (V)u)) visit((V)u);
+		for (uint64_t u = 0; u < n; u++) if (colour[u] == 0 && !cg::contiguous_in(g, (V)u)) visit((V)u);
 		for (uint64_t u = 0; u < n; u++) if (colour[u] == 0) visit((V)u);
 		return order;
 	}
@@ -293,8 +267,8 @@ class Run {
 		if (last - first == 2) return false;          // unambiguous edge
 		if (*first == (last[-1] ^ 1)) return false;   // palindrome
 		std::set<V> targets(first, first + 1), sources(last - 1, last), bubble(first, last);
-		for (const V* it = first; it != last - 1; ++it) for (const abgrr::Edge& e : g.adj[*it]) targets.insert(e.v);
-		for (const V* it = first + 1; it != last; ++it) for (const abgrr::Edge& e : g.adj[*it ^ 1]) sources.insert(e.v ^ 1);
+		for (const V* it = first; it != last - 1; ++it) for (const cg::Edge& e : g.adj[*it]) targets.insert(e.v);
+		for (const V* it = first + 1; it != last; ++it) for (const cg::Edge& e : g.adj[*it ^ 1]) sources.insert(e.v ^ 1);
 		return sources == bubble && targets == bubble;
 	}
 
@@ -337,7 +311,7 @@ class Run {
 		if (g.out_degree(v1) != 1) return NOT_SIMPLE;
 		tail = g.adj[v1][0].v;
 		if (v == (tail ^ 1) || g.in_degree(tail) != nbranches) return NOT_SIMPLE;
-		for (const abgrr::Edge& e : g.adj[v]) {
+		for (const cg::Edge& e : g.adj[v]) {
 			if (g.out_degree(e.v) != 1 || g.in_degree(e.v) != 1) return NOT_SIMPLE;
 			if (g.adj[e.v][0].v != tail) return NOT_SIMPLE;
 		}
@@ -345,14 +319,14 @@ class Run {
 		if (nbranches > opt.maxBranches) return TOO_MANY;
 		minLength = UINT_MAX;
 		maxLength = 0;
-		for (const abgrr::Edge& e : g.adj[v]) { minLength = std::min(minLength, g.length[e.v]); maxLength = std::max(maxLength, g.length[e.v]); }
+		for (const cg::Edge& e : g.adj[v]) { minLength = std::min(minLength, g.length[e.v]); maxLength = std::max(maxLength, g.length[e.v]); }
 		return maxLength >= opt.maxLength ? TOO_LONG : SIMPLE;
 	}
 
 	std::vector<V> key_of(V v) const
 	{
 		std::vector<V> key(1, v);
-		for (const abgrr::Edge& e : g.adj[v]) key.push_back(e.v);
+		for (const cg::Edge& e : g.adj[v]) key.push_back(e.v);
 		return key;
 	}
 
@@ -380,7 +354,7 @@ class Run {
 		for (size_t i = 0; i < n; i++) {
 			const V b = g.adj[t][i].v;
 			if ((b >> 1) >= contigs.size()) fail("`" + opt.contigsPath + "' lacks contig `" + g.cname(b) + "'");
-			const std::string s = (b & 1) ? abgrr::reverse_complement(contigs[b >> 1]) : contigs[b >> 1];
+			const std::string s = (b & 1) ? cg::reverse_complement(contigs[b >> 1]) : contigs[b >> 1];
 			const int len = (int)s.size(), l = -inDists[i], r = -outDists[i];
 			if (l < 0 || r < 0 || len <= l + r)
 				fail("contig `" + g.cname(b) + "' of " + std::to_string(len) + " bases is no longer than its overlaps of " + std::to_string(l) + " and " + std::to_string(r));
@@ -443,7 +417,7 @@ class Run {
 	void pop_bubble(V v, V tail)
 	{
 		std::vector<V> sorted;
-		for (const abgrr::Edge& e : g.adj[v]) sorted.push_back(e.v);
+		for (const cg::Edge& e : g.adj[v]) sorted.push_back(e.v);
 		std::sort(sorted.begin(), sorted.end(), [this](V a, V b) { return g.coverage[a] > g.coverage[b]; });
 		if (opt.bubbleGraph) {
 			printf("\"%s\" -> {", g.vname(v).c_str());
@@ -461,7 +435,7 @@ class Run {
 		if (simple_tests(v, tail, minLength, maxLength, true) != SIMPLE) { count.notSimple++; return false; }
 		if (opt.verbose > 2) {
 			fprintf(stderr, "\n* %s ->", g.vname(v).c_str());
-			for (const abgrr::Edge& e : g.adj[v]) fprintf(stderr, " %s", g.vname(e.v).c_str());
+			for (const cg::Edge& e : g.adj[v]) fprintf(stderr, " %s", g.vname(e.v).c_str());
 			fprintf(stderr, " -> %s\n", g.vname(tail).c_str());
 		}
 		const int verdict = simple_tests(v, tail, minLength, maxLength);
@@ -490,7 +464,7 @@ class Run {
 		std::map<V, int> distance;
 		distance[topo.front()] = 0;
 		for (V u : topo)
-			for (const abgrr::Edge& e : g.adj[u]) {
+			for (const cg::Edge& e : g.adj[u]) {
 				const int weight = e.d + (int)g.length[e.v];
 				if (weight < 0) fail("invalid edge: " + g.vname(u) + " -> " + g.vname(e.v) + " [d=" + std::to_string(e.d) + "]");
 				const int du = distance[u];
@@ -513,15 +487,14 @@ class Run {
 	// assemble_if over the whole graph (ContigGraphAlgorithms.h:194-216) with pred0 = True (assemble) or IsPositive (assemble_stranded)
 	std::vector<std::vector<V>> assemble()
 	{
-		typedef abgrr::Resolver R;
 		std::vector<std::vector<V>> paths;
 		auto pred = [this](V u, V v) { return u != (v ^ 1) && (!opt.ss || (!(u & 1) && !(v & 1))); };
 		const uint64_t nv0 = g.nv();
 		for (uint64_t ui = 0; ui < nv0; ui++) {
 			V u = (V)ui;
-			if (!R::contiguous_out(g, u) || R::contiguous_in(g, u) || !pred(u, g.adj[u][0].v)) continue;
+			if (!cg::contiguous_out(g, u) || cg::contiguous_in(g, u) || !pred(u, g.adj[u][0].v)) continue;
 			std::vector<V> path;
-			while (R::contiguous_out(g, u)) {
+			while (cg::contiguous_out(g, u)) {
 				const V v = g.adj[u][0].v;
 				if (!pred(u, v)) break;
 				path.push_back(u);
@@ -535,8 +508,8 @@ class Run {
 				c += g.coverage[path[i]];
 			}
 			const V nu = g.add_vertex(l, c); // merge
-			R::copy_out_edges(g, path.front() ^ 1, nu ^ 1);
-			R::copy_out_edges(g, path.back(), nu);
+			cg::copy_out_edges(g, path.front() ^ 1, nu ^ 1);
+			cg::copy_out_edges(g, path.back(), nu);
 			for (V x : path) g.clear_vertex(x);
 			for (V x : path) g.remove_vertex(x);
 			paths.push_back(path);

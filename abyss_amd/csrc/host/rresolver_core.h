@@ -15,9 +15,7 @@
 //   RResolver/BloomFilters.cpp:139-209,211-297   loadReads, buildFilters
 //   RResolver/Contigs.cpp                    sequences, comments, loadContigs / storeContigs, assembleContigs
 //   RResolver/SequenceTree.cpp               getTreeSequences
-//   Graph/DirectedGraph.h, ContigGraph.h     adjacency lists in insertion order; (u,v) implies (~v,~u)
-//   Graph/ContigGraphAlgorithms.h:40-240     contiguous_out/in, assemble_if, merge, copy_in/out_edges
-//   Graph/DotIO.h:150-309, AdjIO.h:99-190    readers;  Common/ContigID.h, Dictionary.h  contig names
+//   Graph/ContigGraphAlgorithms.h:118-240    assemble_if, merge (the graph, its readers and copy_in/out_edges are contig_graph.h's)
 // How it differs in structure: the reference tests one candidate sequence at a time against the filter as it walks the
 // repeats (OpenMP tasks).  Whether a combination can be tested at all depends on lengths only, so here a pass first lists
 // every sequence to test (in the reference's -j1 order, random_shuffle calls included), the filter answers them all in ONE
@@ -25,8 +23,9 @@
 // of the reference at -j1.  -e (error correction with btllib's SeedBloomFilter) is not offered.
 #pragma once
 
+#include "contig_graph.h"
 #include "fasta_reader.h"
-#include "graph_writers.h"
+#include "host_cli.h"
 #include "si_bytes.h"
 
 #include <algorithm>
@@ -56,6 +55,8 @@ namespace abgrr {
 #define ABG_RR_PROGRAM "abyss-rresolver-short"
 
 using abgio::ADJ; using abgio::ASQG; using abgio::DOT; using abgio::GFA1; using abgio::GFA2; using abgio::SAM;
+using cg::V; using cg::Edge; using cg::Graph; using cg::die; using cg::print_graph_stats; using cg::reverse_complement;
+using cg::contiguous_out; using cg::contiguous_in; using cg::copy_out_edges;
 
 // RAlgorithmsShort.h:15-28, BloomFilters.h:12
 const int MIN_MARGIN = 2;
@@ -149,11 +150,7 @@ static const char USAGE_MESSAGE[] =
 // main's option loop and check_options, RResolverShort.cpp:170-376.  Returns false when the caller should exit with `*status`.
 inline bool parse_options(int argc, char** argv, Options& o, int* status)
 {
-	{
-		std::ostringstream ss;
-		for (int i = 0; i < argc; i++) ss << (i ? " " : "") << argv[i];
-		o.commandLine = ss.str();
-	}
+	o.commandLine = cli::command_line(argc, argv);
 	enum { OPT_HELP = 1, OPT_VERSION, OPT_GPU };
 	static int format = ADJ, errorCorrection = 0;
 	static const struct option longopts[] = {
@@ -182,8 +179,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 		case 'b': {
 			uint64_t b = 0;
 			if (!si_to_bytes(optarg, &b)) { // (SIToBytes leaves the stream failed: the check below)
-				fprintf(stderr, ABG_RR_PROGRAM ": invalid option: `-%c%s'\n", (char)c, optarg);
-				*status = EXIT_FAILURE;
+				*status = cli::invalid_option(ABG_RR_PROGRAM, c, optarg);
 				return false;
 			}
 			o.bloomSize = (size_t)b;
@@ -216,8 +212,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 		case OPT_GPU: arg >> o.device; break;
 		}
 		if (optarg != NULL && c != 'b' && (!arg.eof() || arg.fail())) {
-			fprintf(stderr, ABG_RR_PROGRAM ": invalid option: `-%c%s'\n", (char)c, optarg);
-			*status = EXIT_FAILURE;
+			*status = cli::invalid_option(ABG_RR_PROGRAM, c, optarg);
 			return false;
 		}
 	}
@@ -234,7 +229,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 	if (o.maxTests > 127) { fprintf(stderr, ABG_RR_PROGRAM ": --max-tests cannot be higher than 127\n"); die = true; } // (int8_t counts: the usage says so, the reference overflows)
 	if (o.errorCorrection) { fprintf(stderr, ABG_RR_PROGRAM ": -e (error correction with spaced seeds) is not supported by this build\n"); die = true; }
 	if (die) {
-		fprintf(stderr, "Try `" ABG_RR_PROGRAM " --help' for more information.\n");
+		cli::try_help(ABG_RR_PROGRAM);
 		*status = EXIT_FAILURE;
 		return false;
 	}
@@ -242,361 +237,6 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 	o.graphPath = argv[optind++];
 	for (int i = optind; i < argc; i++) o.readFiles.push_back(argv[i]);
 	return true;
-}
-
-[[noreturn]] inline void die(const std::string& msg)
-{
-	fprintf(stderr, "%s\n", msg.c_str());
-	exit(EXIT_FAILURE);
-}
-
-// ---- the contig graph: ContigGraph<DirectedGraph<ContigProperties, Distance>> + g_contigNames -------------------------
-typedef uint32_t V; // vertex = 2 * contig + sense (ContigNode)
-struct Edge { V v; int d; };
-
-struct Graph {
-	unsigned k = 0;
-	std::vector<std::vector<Edge>> adj; // out-edges in insertion order
-	std::vector<unsigned> length, coverage; // per VERTEX (the reference keeps a copy of the properties on both)
-	std::vector<bool> rem;
-	// g_contigNames + g_nextContigName (Common/ContigID.h, Dictionary.h)
-	std::vector<std::string> names;
-	std::unordered_map<std::string, unsigned> index;
-	unsigned nextName = 0;
-
-	uint64_t nv() const { return adj.size(); }
-	bool removed(uint64_t u) const { return u < rem.size() && rem[u]; }
-	const std::string& cname(uint64_t u) const { return names[u >> 1]; }
-	unsigned len(uint64_t u) const { return length[u]; }
-	unsigned cov(uint64_t u) const { return coverage[u]; }
-	template <class F> void for_out(uint64_t u, F f) const { for (const Edge& e : adj[u]) f(e.v, e.d); }
-	std::string vname(V u) const { return names[u >> 1] + ((u & 1) ? '-' : '+'); }
-
-	// Dictionary::put (Dictionary.h:48-60) through put(vertex_name, ...) (ContigNode.h:236-247)
-	void put_name(V u, std::string name)
-	{
-		const char c = name.empty() ? 0 : name[name.size() - 1];
-		if (c == '+' || c == '-') name.erase(name.size() - 1);
-		const unsigned id = u >> 1;
-		if (id < names.size()) {
-			if (names[id] != name) die("error: the names of vertex " + std::to_string(u) + " do not agree: `" + names[id] + "', `" + name + "'");
-			return;
-		}
-		if (id != names.size()) die("error: vertices out of order near `" + name + "'");
-		if (!index.emplace(name, id).second) { fprintf(stderr, "error: duplicate ID: `%s'\n", name.c_str()); exit(EXIT_FAILURE); }
-		names.push_back(name);
-	}
-	// find_vertex (ContigNode.h:283-303)
-	V find_vertex(std::string name) const
-	{
-		if (name.size() < 2) die("error: unexpected ID: `" + name + "'");
-		const char c = name[name.size() - 1];
-		name.erase(name.size() - 1);
-		if (c != '+' && c != '-') die("error: unexpected ID: `" + name + c + "'");
-		return find_contig(name) * 2 + (c == '-');
-	}
-	unsigned find_contig(const std::string& name) const
-	{
-		auto it = index.find(name);
-		if (it == index.end()) { fprintf(stderr, "error: unexpected ID: `%s'\n", name.c_str()); exit(EXIT_FAILURE); }
-		return it->second;
-	}
-	// createContigName / setNextContigName (ContigID.h:31-61)
-	std::string create_name()
-	{
-		if (nextName == 0) {
-			unsigned mx = 0;
-			for (const std::string& s : names) {
-				std::istringstream iss(s);
-				unsigned x;
-				if (iss >> x && iss.eof() && x > mx) mx = x;
-			}
-			nextName = names.empty() ? 0 : 1 + mx;
-		}
-		return std::to_string(nextName++);
-	}
-
-	// DirectedGraph
-	V add_vertex1(unsigned l, unsigned c) { adj.emplace_back(); length.push_back(l); coverage.push_back(c); return (V)(adj.size() - 1); }
-	void add_edge1(V u, V v, int d) { adj[u].push_back(Edge{ v, d }); }
-	void remove_edge1(V u, V v)
-	{
-		auto& e = adj[u];
-		e.erase(std::remove_if(e.begin(), e.end(), [v](const Edge& x) { return x.v == v; }), e.end());
-	}
-	const Edge* find_edge(V u, V v) const
-	{
-		for (const Edge& e : adj[u]) if (e.v == v) return &e;
-		return nullptr;
-	}
-	bool has_edge(V u, V v) const { return find_edge(u, v) != nullptr; }
-	// get(edge_bundle, g, u, v) (ContigProperties.h:187-205)
-	int dist(V u, V v) const
-	{
-		const Edge* e = find_edge(u, v);
-		if (!e) die("error: no edge " + vname(u) + " -> " + vname(v));
-		return e->d;
-	}
-	unsigned out_degree(V u) const { return (unsigned)adj[u].size(); }
-	uint64_t num_edges() const { uint64_t n = 0; for (auto& a : adj) n += a.size(); return n; }
-	// ContigGraph (ContigGraph.h:124-228)
-	unsigned in_degree(V u) const { return (unsigned)adj[u ^ 1].size(); }
-	V add_vertex(unsigned l, unsigned c) { const V v = add_vertex1(l, c); add_vertex1(l, c); return v; }
-	void add_edge(V u, V v, int d) { add_edge1(u, v, d); if (u != (v ^ 1)) add_edge1(v ^ 1, u ^ 1, d); }
-	void remove_edge(V u, V v) { remove_edge1(u, v); if (u != (v ^ 1)) remove_edge1(v ^ 1, u ^ 1); }
-	void clear_out_edges(V u)
-	{
-		for (const Edge& e : adj[u]) if ((e.v ^ 1) != u) remove_edge1(e.v ^ 1, u ^ 1);
-		adj[u].clear();
-	}
-	void clear_vertex(V v) { clear_out_edges(v); clear_out_edges(v ^ 1); }
-	void remove_vertex(V v)
-	{
-		if (rem.size() < adj.size()) rem.resize(adj.size(), false);
-		rem[v] = true;
-		rem[v ^ 1] = true;
-	}
-	uint64_t num_removed() const { uint64_t n = 0; for (uint64_t u = 0; u < nv(); u++) n += removed(u); return n; }
-};
-
-inline void print_graph_stats(FILE* out, const Graph& g)
-{
-	std::map<int, uint64_t> h;
-	for (uint64_t u = 0; u < g.nv(); u++) if (!g.removed(u)) h[(int)g.out_degree((V)u)]++;
-	abgio::print_graph_stats(out, (unsigned)(g.nv() - g.num_removed()), (unsigned)g.num_edges(), h);
-}
-
-// ---- readers ---------------------------------------------------------------------------------------------------
-// A cursor over the whole file with the stream manipulators the reference parses with (Common/IOUtil.h:38-84)
-struct Cursor {
-	const std::string& s;
-	size_t p = 0;
-	explicit Cursor(const std::string& s) : s(s) {}
-	bool eof() const { return p >= s.size(); }
-	int peek() const { return eof() ? EOF : (unsigned char)s[p]; }
-	void ws() { while (!eof() && isspace((unsigned char)s[p])) p++; }
-	void expect(const char* pat) // operator>>(istream&, expect)
-	{
-		for (const char* q = pat; *q; ++q) {
-			if (*q == ' ') { ws(); continue; }
-			if (eof() || s[p] != *q) {
-				fprintf(stderr, "error: Expected `%s' and saw ", q);
-				if (eof()) fprintf(stderr, "end-of-file\n");
-				else {
-					const size_t e = s.find('\n', p);
-					fprintf(stderr, "`%c'\nnear: %s\n", s[p], s.substr(p, e == std::string::npos ? e : e - p).c_str());
-				}
-				exit(EXIT_FAILURE);
-			}
-			p++;
-		}
-	}
-	void ignore(char delim) { const size_t e = s.find(delim, p); p = e == std::string::npos ? s.size() : e + 1; }
-	bool number(long long& x) // operator>>(int): leading whitespace, sign, digits
-	{
-		ws();
-		size_t q = p;
-		if (q < s.size() && (s[q] == '-' || s[q] == '+')) q++;
-		if (q >= s.size() || !isdigit((unsigned char)s[q])) return false;
-		x = strtoll(s.c_str() + p, nullptr, 10);
-		while (q < s.size() && isdigit((unsigned char)s[q])) q++;
-		p = q;
-		return true;
-	}
-	unsigned uns(const char* what) { long long x; if (!number(x) || x < 0) die(std::string("error: expected a number (") + what + ")"); return (unsigned)x; }
-	int integer(const char* what) { long long x; if (!number(x)) die(std::string("error: expected a number (") + what + ")"); return (int)x; }
-	bool quoted(std::string& out) // read_dot_name
-	{
-		ws();
-		if (peek() != '"') return false;
-		p++;
-		const size_t e = s.find('"', p);
-		out = s.substr(p, e == std::string::npos ? e : e - p);
-		p = e == std::string::npos ? s.size() : e + 1;
-		return true;
-	}
-};
-// operator>>(istream&, ContigProperties&) (ContigProperties.h:112-126) and Distance (:160-168)
-inline void read_props(Cursor& in, unsigned& l, unsigned& c)
-{
-	in.ws();
-	if (in.peek() == 'l') {
-		in.expect("l =");
-		l = in.uns("l");
-		in.ws();
-		if (in.peek() == 'C') { in.expect("C ="); c = in.uns("C"); }
-	} else if (in.peek() == 'C') {
-		in.expect("C=");
-		c = in.uns("C");
-		in.expect(", l=");
-		l = in.uns("l");
-	} else {
-		l = in.uns("length");
-		c = in.uns("coverage");
-	}
-}
-inline int read_distance(Cursor& in)
-{
-	in.expect(" d = ");
-	if (in.peek() == '"') { in.expect("\""); const int d = in.integer("d"); in.expect("\""); return d; }
-	return in.integer("d");
-}
-
-// read_dot (Graph/DotIO.h:150-309) on the plain directed graph: every line of the file is one vertex or one edge
-inline void read_dot(const std::string& text, Graph& g, Options& o)
-{
-	Cursor in(text);
-	in.ws();
-	in.expect("digraph");
-	in.ignore('{');
-	int defd = -(int)o.k + 1;
-	for (bool done = false; !done;) {
-		in.ws();
-		if (in.eof()) break;
-		switch (in.peek()) {
-		case 'g':
-			in.expect("graph [ ");
-			if (in.peek() == 'k') {
-				in.expect("k =");
-				const unsigned k = in.uns("k");
-				if (o.k > 0 && k != o.k) die("error: the graph was built with k=" + std::to_string(k) + ", not " + std::to_string(o.k));
-				o.k = k;
-				defd = -(int)o.k + 1;
-			}
-			in.ignore(']');
-			break;
-		case 'e':
-			in.expect("edge [");
-			defd = read_distance(in);
-			in.ignore(']');
-			break;
-		default: done = true; break;
-		}
-		in.ws();
-		if (in.peek() == ';') in.p++;
-	}
-	const bool addVertices = g.nv() == 0;
-	for (std::string uname; in.quoted(uname);) {
-		in.ws();
-		if (in.eof()) die("error: unexpected end of the graph file");
-		const char c = in.s[in.p++];
-		if (c == ';' || c == '[') {
-			unsigned l = 0, cv = 0;
-			if (c == '[') { read_props(in, l, cv); in.ignore(']'); }
-			if (addVertices) { const V u = g.add_vertex1(l, cv); g.put_name(u, uname); }
-			else {
-				const V u = g.find_vertex(uname);
-				if (c == '[' && (g.length[u] != l || g.coverage[u] != cv)) die("error: vertex properties do not agree: \"" + uname + "\"");
-			}
-		} else if (c == '-') {
-			in.expect(">");
-			const V u = g.find_vertex(uname);
-			in.ws();
-			if (in.peek() == '{') {
-				in.expect("{");
-				for (std::string vn; in.quoted(vn);) g.add_edge1(u, g.find_vertex(vn), defd);
-				in.expect(" }");
-			} else {
-				std::string vn;
-				if (!in.quoted(vn)) { fprintf(stderr, "error: Expected `\"' and saw `%c'.\n", (char)in.peek()); exit(EXIT_FAILURE); }
-				const V v = g.find_vertex(vn);
-				int d = defd;
-				in.ws();
-				if (in.peek() == '[') { in.expect("["); d = read_distance(in); in.ignore(']'); }
-				if (g.has_edge(u, v)) { // DisallowParallelEdges, GraphIO.h:84-92
-					fprintf(stderr, "error: parallel edges: [d=%d], [d=%d]\n", g.dist(u, v), d);
-					exit(EXIT_FAILURE);
-				}
-				g.add_edge1(u, v, d);
-			}
-		} else {
-			fprintf(stderr, "error: Expected `[' or `->' and saw `%c'.\n", c);
-			exit(EXIT_FAILURE);
-		}
-		in.ws();
-		if (in.peek() == ';') in.p++;
-	}
-	in.expect("}");
-	in.ws();
-	if (!in.eof()) die("error: Expected end-of-file after the graph");
-	if (g.nv() == 0) die("error: the graph has no vertices");
-}
-
-// read_adj (Graph/AdjIO.h:99-190), ADJ format: "name length coverage\t; out-edges\t; in-edges"
-inline void read_adj(const std::string& text, Graph& g, const Options& o)
-{
-	const int defd = -(int)o.k + 1;
-	std::vector<std::pair<size_t, size_t>> lines; // [begin, end)
-	for (size_t a = 0; a < text.size();) {
-		size_t e = text.find('\n', a);
-		if (e == std::string::npos) e = text.size();
-		if (e > a) lines.push_back({ a, e });
-		a = e + 1;
-	}
-	if (lines.empty()) die("error: the graph file is empty");
-	{
-		const std::string first = text.substr(lines[0].first, lines[0].second - lines[0].first);
-		if (std::count(first.begin(), first.end(), ';') != 2) die("error: the graph is neither GraphViz nor ADJ format (the formats this build reads)");
-	}
-	for (auto& ln : lines) {
-		std::istringstream ss(text.substr(ln.first, ln.second - ln.first));
-		std::string name;
-		unsigned l = 0, c = 0;
-		if (!(ss >> name >> l >> c)) die("error: malformed ADJ line");
-		const V u = g.add_vertex(l, c);
-		g.put_name(u, name);
-	}
-	for (auto& ln : lines) {
-		const std::string line = text.substr(ln.first, ln.second - ln.first);
-		const size_t s1 = line.find(';'), s2 = line.find(';', s1 + 1);
-		std::istringstream head(line.substr(0, s1));
-		std::string name;
-		head >> name;
-		const V u = 2 * g.find_contig(name);
-		for (unsigned sense = 0; sense < 2; sense++) {
-			std::string part = sense == 0 ? line.substr(s1 + 1, s2 - s1 - 1) : line.substr(s2 + 1);
-			Cursor in(part);
-			for (;;) {
-				in.ws();
-				if (in.eof()) break;
-				size_t e = in.p;
-				while (e < part.size() && !isspace((unsigned char)part[e])) e++;
-				const std::string vn = part.substr(in.p, e - in.p);
-				in.p = e;
-				in.ws();
-				const V v = g.find_vertex(vn);
-				int d = defd;
-				if (in.peek() == '[') { in.p++; d = read_distance(in); in.ignore(']'); }
-				if (g.has_edge(u ^ sense, v ^ sense)) die("error: parallel edges in the ADJ file near `" + vn + "'");
-				g.add_edge1(u ^ sense, v ^ sense, d);
-			}
-		}
-	}
-}
-
-inline std::string slurp(const std::string& path)
-{
-	std::ifstream f(path, std::ios::binary);
-	if (!f.good()) { fprintf(stderr, "error: `%s': %s\n", path.c_str(), strerror(errno)); exit(EXIT_FAILURE); }
-	std::ostringstream ss;
-	ss << f.rdbuf();
-	return ss.str();
-}
-
-inline std::string reverse_complement(const std::string& s)
-{
-	std::string r(s.rbegin(), s.rend());
-	for (auto& c : r) {
-		switch (c) { // complementBaseChar, Common/Sequence.cpp:21-47
-		case 'A': c = 'T'; break; case 'C': c = 'G'; break; case 'G': c = 'C'; break; case 'T': c = 'A'; break;
-		case 'a': c = 't'; break; case 'c': c = 'g'; break; case 'g': c = 'c'; break; case 't': c = 'a'; break;
-		case 'N': case 'n': case '.': break;
-		case 'M': c = 'K'; break; case 'R': c = 'Y'; break; case 'W': case 'S': break; case 'Y': c = 'R'; break; case 'K': c = 'M'; break;
-		case 'V': c = 'B'; break; case 'H': c = 'D'; break; case 'D': c = 'H'; break; case 'B': c = 'V'; break;
-		default: fprintf(stderr, "error: unexpected character: `%c'\n", c); exit(EXIT_FAILURE);
-		}
-	}
-	return r;
 }
 
 // ---- supports and read sizes (RAlgorithmsShort.h:85-187) -----------------------------------------------------
@@ -666,17 +306,7 @@ class Resolver {
 	void load_graph()
 	{
 		if (opt.verbose) fprintf(stderr, "Loading contig graph from `%s'...\n", opt.graphPath.c_str());
-		const std::string text = slurp(opt.graphPath);
-		size_t p = 0;
-		while (p < text.size() && isspace((unsigned char)text[p])) p++;
-		const int c = p < text.size() ? text[p] : EOF;
-		g.k = opt.k;
-		if (c == 'd') read_dot(text, g, opt);
-		else if (c == '@' || c == 'H' || c == '>' || c == 'g')
-			die("error: `" + opt.graphPath + "': this build reads the contig graph in GraphViz (--dot) or ADJ format only");
-		else read_adj(text, g, opt);
-		g.k = opt.k;
-		if (g.nv() & 1) die("error: `" + opt.graphPath + "': a contig is missing one of its two vertices");
+		cg::load_graph(opt.graphPath, opt.k, g, [](const std::string& msg) { die("error: " + msg); });
 		if (opt.verbose) { fprintf(stderr, "Contig graph loaded.\n"); print_graph_stats(stderr, g); }
 	}
 	void load_contigs()
@@ -771,20 +401,6 @@ class Resolver {
 	}
 
 	// assemble_if + merge (ContigGraphAlgorithms.h:118-240) on a copy, then assembleContigs (Contigs.cpp:199-258)
-	static bool contiguous_out(const Graph& h, V u) { return h.out_degree(u) == 1 && h.in_degree(h.adj[u][0].v) == 1; }
-	static bool contiguous_in(const Graph& h, V u) { return contiguous_out(h, u ^ 1); }
-	static void copy_out_edges(Graph& h, V u, V uout)
-	{
-		bool palindrome = false;
-		int pd = 0;
-		const size_t n = h.adj[u].size(); // (u's own list does not change in here)
-		for (size_t i = 0; i < n; i++) {
-			const Edge e = h.adj[u][i];
-			if ((e.v ^ 1) == u) { palindrome = true; pd = e.d; }
-			else h.add_edge(uout, e.v, e.d);
-		}
-		if (palindrome) { h.add_edge(uout, u ^ 1, pd); h.add_edge(uout, uout ^ 1, pd); }
-	}
 	void assemble_contigs()
 	{
 		if (opt.verbose) fprintf(stderr, "Assembling contigs... ");

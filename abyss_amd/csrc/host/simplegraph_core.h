@@ -20,7 +20,7 @@
 // nothing.
 //
 // Where the reference aborts or trips an assert, this prints an error naming the input and exits 1: a name the graph lacks, a
-// malformed estimate, an output file that cannot be opened.  The graph is read in the ADJ and GraphViz formats (rresolver_core.h's
+// malformed estimate, an output file that cannot be opened.  The graph is read in the ADJ and GraphViz formats (contig_graph.h's
 // readers); the others are refused.
 #pragma once
 
@@ -36,7 +36,7 @@ namespace sg {
 
 #define ABG_SG_PROGRAM "SimpleGraph"
 
-using abgrr::V;
+using cg::V; using cg::Node; using cg::Path;
 
 static const char VERSION_MESSAGE[] =
     ABG_SG_PROGRAM " (ABySS) " ABG_IO_VERSION "\n"
@@ -132,8 +132,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 		case OPT_DB: case OPT_LIBRARY: case OPT_STRAIN: case OPT_SPECIES: arg >> ignored; break; // (this build keeps no database)
 		}
 		if (optarg != NULL && !arg.eof()) {
-			fprintf(stderr, ABG_SG_PROGRAM ": invalid option: `-%c%s'\n", (char)c, optarg);
-			*status = EXIT_FAILURE;
+			*status = cli::invalid_option(ABG_SG_PROGRAM, c, optarg);
 			return false;
 		}
 	}
@@ -143,7 +142,7 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 	if (argc - optind < 2) { fprintf(stderr, ABG_SG_PROGRAM ": missing arguments\n"); die = true; }
 	else if (argc - optind > 2) { fprintf(stderr, ABG_SG_PROGRAM ": too many arguments\n"); die = true; }
 	if (die) {
-		fprintf(stderr, "Try `" ABG_SG_PROGRAM " --help' for more information.\n");
+		cli::try_help(ABG_SG_PROGRAM);
 		*status = EXIT_FAILURE;
 		return false;
 	}
@@ -152,19 +151,12 @@ inline bool parse_options(int argc, char** argv, Options& o, int* status)
 	return true;
 }
 
-[[noreturn]] inline void fail(const std::string& msg)
-{
-	fflush(stdout);
-	fprintf(stderr, ABG_SG_PROGRAM ": error: %s\n", msg.c_str());
-	exit(EXIT_FAILURE);
-}
+[[noreturn]] inline void fail(const std::string& msg) { cli::fail(ABG_SG_PROGRAM, msg); }
 
 struct Est { int distance = 0; unsigned numPairs = 0; float stdDev = 0; }; // DistanceEst, Estimate.h:26-38
 typedef std::vector<std::pair<V, Est>> Estimates;
 struct Record { unsigned ref = 0; Estimates est[2]; }; // EstimateRecord, Estimate.h:162-198
 
-typedef int32_t Node; // ContigNode: a vertex, or -n for the ambiguous node of n bases (ContigNode.h:41-48)
-typedef std::vector<Node> Path;
 typedef std::vector<Path> Paths;
 
 struct Stats { unsigned seedTooShort = 0, noEdges = 0, edgesRemoved = 0, totalAttempted = 0, uniqueEnd = 0, noPossiblePaths = 0, noValidPaths = 0,
@@ -175,7 +167,7 @@ class Run {
 	Run(Options& o, Searcher& s) : opt(o), searcher(s) {}
 	Options& opt;
 	Searcher& searcher;
-	abgrr::Graph graph;
+	cg::Graph graph;
 	Stats stats;
 	unsigned minNumPairs = UINT_MAX, minNumPairsUsed = UINT_MAX; // g_minNumPairs, g_minNumPairsUsed
 	FILE* out = nullptr;
@@ -188,24 +180,6 @@ class Run {
 
 	// allowedError, Estimate.h:154-159
 	unsigned allowed_error(float stddev) const { return (unsigned)ceilf(3 * stddev + opt.distanceError); }
-
-	void read_graph()
-	{
-		const std::string text = abgrr::slurp(opt.adjPath);
-		size_t p = 0;
-		while (p < text.size() && isspace((unsigned char)text[p])) p++;
-		const int c = p < text.size() ? text[p] : EOF;
-		abgrr::Options ro;
-		ro.k = opt.k;
-		graph.k = opt.k;
-		if (c == 'd') abgrr::read_dot(text, graph, ro);
-		else if (c == '@' || c == 'H' || c == '>' || c == 'g')
-			fail("`" + opt.adjPath + "': this build reads the contig graph in GraphViz (--dot) or ADJ format only");
-		else abgrr::read_adj(text, graph, ro);
-		opt.k = ro.k;
-		graph.k = opt.k;
-		if (graph.nv() & 1) fail("`" + opt.adjPath + "': a contig is missing one of its two vertices");
-	}
 
 	// the records of the .dist file, through the reader Overlap uses (overlap_core.h)
 	void read_dist(const std::string& text, std::vector<Record>& records)
@@ -221,13 +195,8 @@ class Run {
 		    [](const std::string& msg) { fail(msg); });
 	}
 
-	std::string name(Node u) const { return u < 0 ? std::to_string(-(int64_t)u) + "N" : graph.vname((V)u); }
-	std::string show(const Path& p) const // operator<<(ostream&, const ContigPath&), ContigPath.h:37-45
-	{
-		std::string s;
-		for (size_t i = 0; i < p.size(); ++i) { if (i) s += ' '; s += name(p[i]); }
-		return s;
-	}
+	std::string name(Node u) const { return cg::node_name(graph, u); }
+	std::string show(const Path& p) const { return cg::show_path(graph, p); }
 	static void appendf(std::string& s, const char* fmt, ...) __attribute__((format(printf, 2, 3)))
 	{
 		char buf[1024];
@@ -456,7 +425,7 @@ class Run {
 		std::vector<uint32_t> targets;
 		std::vector<int32_t> distances;
 		for (uint64_t u = 0; u < graph.nv(); ++u) {
-			for (const abgrr::Edge& e : graph.adj[u]) { targets.push_back(e.v); distances.push_back(e.d); }
+			for (const cg::Edge& e : graph.adj[u]) { targets.push_back(e.v); distances.push_back(e.d); }
 			eoff.push_back(targets.size());
 		}
 		if (!searcher.set_graph(eoff, graph.length, targets, distances, err)) fail(err);
@@ -466,10 +435,10 @@ class Run {
 	int run()
 	{
 		if (opt.verbose > 0) fprintf(stderr, "Reading `%s'...\n", opt.adjPath.c_str());
-		read_graph();
-		if (opt.verbose > 0) abgrr::print_graph_stats(stdout, graph);
+		cg::load_graph(opt.adjPath, opt.k, graph, fail);
+		if (opt.verbose > 0) cg::print_graph_stats(stdout, graph);
 		if (opt.verbose > 0) fprintf(stderr, "Reading `%s'...\n", opt.estPath.c_str());
-		const std::string text = abgrr::slurp(opt.estPath);
+		const std::string text = cg::slurp(opt.estPath);
 		out = fopen(opt.out.c_str(), "wb");
 		if (!out) { fflush(stdout); fprintf(stderr, "error: `%s': %s\n", opt.out.c_str(), strerror(errno)); return EXIT_FAILURE; }
 		std::vector<Record> records;

@@ -9,29 +9,16 @@ import random
 import re
 import struct
 import subprocess
-import tarfile
 
 import numpy as np
 
+import golden_archive
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-GOLDEN = os.path.join(HERE, "golden", "distanceest")
 JOB = np.dtype([("first", "<i4"), ("last", "<i4"), ("len0", "<u4"), ("len1", "<u4")])
 PAIR = np.dtype([("first", "<i4"), ("last", "<i4"), ("len0", "<u4"), ("len1", "<u4"), ("l", "<u4"), ("rf", "<u4")])
 
-
-@functools.lru_cache(maxsize=None)
-def _data():
-    with tarfile.open(os.path.join(GOLDEN, "data.tar.gz"), "r:gz") as tar:
-        return {m.name: tar.extractfile(m).read() for m in tar.getmembers()}
-
-
-def golden(name):
-    return _data()[name]
-
-
-@functools.lru_cache(maxsize=None)
-def cases():
-    return json.load(open(os.path.join(GOLDEN, "cases.json")))
+_files, golden, cases = golden_archive.bind("distanceest")
 
 
 def rules():

@@ -4,27 +4,12 @@ import functools
 import io
 import json
 import os
-import tarfile
 
+import golden_archive
 from util import GOLDEN
 
 KN = os.path.join(GOLDEN, "konnector")
-
-
-@functools.lru_cache(maxsize=None)
-def cases():
-    return json.load(open(os.path.join(KN, "cases.json")))
-
-
-@functools.lru_cache(maxsize=None)
-def files():
-    """name -> bytes of every file in data.tar.gz"""
-    with tarfile.open(os.path.join(KN, "data.tar.gz"), "r:gz") as tar:
-        return {m.name: tar.extractfile(m).read() for m in tar.getmembers() if m.isfile()}
-
-
-def golden(name):
-    return files()[name]
+files, golden, cases = golden_archive.bind("konnector")
 
 
 def hash_vectors():

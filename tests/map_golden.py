@@ -3,31 +3,13 @@ outputs packed in data.tar.gz; and the one input too large to commit, the 2 Mbp 
 (the goldens hold the digests of its index files and the SAM of its reads)."""
 import functools
 import hashlib
-import json
-import os
 import struct
-import tarfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-MAP = os.path.join(HERE, "golden", "map")
+import golden_archive
 
-
-@functools.lru_cache(maxsize=None)
-def cases():
-    return json.load(open(os.path.join(MAP, "cases.json")))
-
-
-@functools.lru_cache(maxsize=None)
-def files():
-    """name -> bytes of every file in data.tar.gz"""
-    with tarfile.open(os.path.join(MAP, "data.tar.gz"), "r:gz") as tar:
-        return {m.name: tar.extractfile(m).read() for m in tar.getmembers() if m.isfile()}
-
-
-def golden(name):
-    return files()[name]
+files, golden, cases = golden_archive.bind("map")
 
 
 def _mix(x):

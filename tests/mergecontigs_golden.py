@@ -9,10 +9,10 @@ import os
 import random
 import re
 import subprocess
-import tarfile
+
+import golden_archive
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-GOLDEN = os.path.join(HERE, "golden", "mergecontigs")
 COMP = bytes.maketrans(b"ACGTacgtMRWSYKVHDBNmrwsykvhdbn", b"TGCAtgcaKYWSRMBDHVNkywsrmbdhvn")
 MASK = {"A": 1, "C": 2, "G": 4, "T": 8, "M": 3, "R": 5, "S": 6, "V": 7, "W": 9, "Y": 10, "H": 11, "K": 12, "D": 13, "B": 14, "N": 15}
 UNMASK = "NACMGRSVTWYHKDBN"
@@ -193,19 +193,7 @@ def py_merge_path(contigs, k, nodes, overlaps, verbose=0, names=None):
 
 # ---- the goldens
 
-@functools.lru_cache(maxsize=None)
-def _data():
-    with tarfile.open(os.path.join(GOLDEN, "data.tar.gz")) as tar:
-        return {m.name: tar.extractfile(m).read() for m in tar.getmembers() if m.isfile()}
-
-
-def golden(name):
-    return _data()[name]
-
-
-@functools.lru_cache(maxsize=None)
-def cases():
-    return json.load(open(os.path.join(GOLDEN, "cases.json")))
+_files, golden, cases = golden_archive.bind("mergecontigs")
 
 
 def rules():

@@ -15,7 +15,8 @@ import random
 import re
 import struct
 import subprocess
-import tarfile
+
+import golden_archive
 
 MATCH, MISMATCH, GAP = 1, -2, -10000
 NEG = float("-inf")
@@ -147,25 +148,12 @@ def random_pair(rng: random.Random, la: int, lb: int, alphabet: str = "ACGT", ra
 # ---- the goldens (tests/golden/mergepairs, written by tests/golden/make_mergepairs.py from the unmodified reference)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-GOLDEN = os.path.join(HERE, "golden", "mergepairs")
 SUFFIXES = ("_merged.fastq", "_reads_1.fastq", "_reads_2.fastq")
 STATS = re.compile(r"total=(\d+) merged=(\d+) unmerged=(\d+) unchaste=(\d+)\nno_alignment=(\d+) too_many_aligns=(\d+) too_few_matches=(\d+) has_indel=(\d+) low_pid=(\d+)\n")
 STAT_NAMES = ("total", "merged", "unmerged", "unchaste", "no_alignment", "too_many_aligns", "too_few_matches", "has_indel", "low_pid")
 
 
-@functools.lru_cache(maxsize=None)
-def _data():
-    with tarfile.open(os.path.join(GOLDEN, "data.tar.gz")) as tar:
-        return {m.name: tar.extractfile(m).read() for m in tar.getmembers() if m.isfile()}
-
-
-def golden(name):
-    return _data()[name]
-
-
-@functools.lru_cache(maxsize=None)
-def cases():
-    return json.load(open(os.path.join(GOLDEN, "cases.json")))
+_files, golden, cases = golden_archive.bind("mergepairs")
 
 
 def needs_no_device(case):

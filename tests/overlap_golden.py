@@ -8,12 +8,12 @@ import random
 import re
 import struct
 import subprocess
-import tarfile
 
 import numpy as np
 
+import golden_archive
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-GOLDEN = os.path.join(HERE, "golden", "overlap")
 COMPLEMENT = str.maketrans("ACGTN.MRWSYKVHDBacgtnmrwsykvhdb", "TGCAN.KYWSRMBDHVtgcankywsrmbdhv")  # Common/Sequence.cpp:21-45
 
 
@@ -28,19 +28,7 @@ def py_find(t, h):
 
 # ---- the goldens
 
-@functools.lru_cache(maxsize=None)
-def _data():
-    with tarfile.open(os.path.join(GOLDEN, "data.tar.gz"), "r:gz") as tar:
-        return {m.name: tar.extractfile(m).read() for m in tar.getmembers()}
-
-
-def golden(name):
-    return _data()[name]
-
-
-@functools.lru_cache(maxsize=None)
-def cases():
-    return json.load(open(os.path.join(GOLDEN, "cases.json")))
+_files, golden, cases = golden_archive.bind("overlap")
 
 
 def rules():

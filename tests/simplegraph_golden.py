@@ -9,12 +9,12 @@ import re
 import struct
 import subprocess
 import sys
-import tarfile
 
 import numpy as np
 
+import golden_archive
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-GOLDEN = os.path.join(HERE, "golden", "simplegraph")
 MAX_COST, MAX_PATHS = 100000, 200
 SATISFIED = 2 ** 31 - 1
 
@@ -119,19 +119,7 @@ class Graph:
 
 # ---- the goldens
 
-@functools.lru_cache(maxsize=None)
-def _data():
-    with tarfile.open(os.path.join(GOLDEN, "data.tar.gz"), "r:gz") as tar:
-        return {m.name: tar.extractfile(m).read() for m in tar.getmembers()}
-
-
-def golden(name):
-    return _data()[name]
-
-
-@functools.lru_cache(maxsize=None)
-def cases():
-    return json.load(open(os.path.join(GOLDEN, "cases.json")))
+_files, golden, cases = golden_archive.bind("simplegraph")
 
 
 def rules():
