@@ -75,7 +75,12 @@ struct Config {
 	uint32_t slice_filter = 0;        // partitioned run: a rank keeps only its own range of the counters and PASS 2 probes the all-gathered
 	                                  // bit plane (B beyond one GPU): 0 = when the whole filter would not fit the device, 1 = always, 2 = never
 	bool solid_plane = true;          // PASS 2 probes the bit plane "counter >= kc" instead of the counters (Engine::ensure_plane)
-	uint32_t classify_slots = 65536;  // lanes of the classification kernel in flight (each owns 22 KB of lookAhead scratch)
+	uint32_t classify_slots = 0;      // lanes of the classification kernel in flight (each owns 22 KB of lookAhead scratch); 0: one per wave slot the kernel
+	                                  // is compiled for (CUs x 4 SIMDs x ABG_CLS_WAVES x 64 = 196,608 on 256 CUs) where its two scratch pools (4.3 GB each)
+	                                  // fit an eighth of the free memory, else 65,536 (Engine::ensure_walk; ABG_CLS_SLOTS overrides).  Round 12, configs[1], three
+	                                  // alternating lines: 65,536 lanes with a static stride (rounds 4-11) PASS 2 262.5-266.0 ms, step 525.2-527.4, 7.9-8.6 ms
+	                                  // a step waiting for the classification (Stats::cls_wait_ms); 196,608 lanes drawing tickets 246.2-253.0, 509.0-516.5,
+	                                  // 0.01 ms.  Either half alone: tickets at 65,536 lanes 254.2-259.7 / 3.3-3.7 ms, 196,608 lanes strided 247.9-249.7 / 0.01 ms.
 	uint32_t cls_both_max_mb = 1024;  // ... for filters whose two-bit array is at most this large
 	bool cls_both = true;             // the classification probes the solid plane and the visited filter in one array of two bits a position (FBothBuild)
 	bool prefetch_classify = true;    // classify batch i + 1 on a side stream while batch i's walkers thin out
@@ -3264,6 +3269,14 @@ struct FPcWrite { // commit order of the records and the contig ids (off = recor
 //   template<int NW> void launch_commit(CommitEnv<NW>, uint32_t c_begin, uint32_t c_end);
 //   void launch_drain(InsertDrainEnv);          // one workgroup running insert_drain
 //   template<class F> void launch_tiles(uint64_t n, F f, const char* name); // f(tile, fast memory [F::FAST bytes], sync): one workgroup per item
+// Optional (a backend without them gets the answer on the right):
+//   uint32_t classify_lanes();                  // lanes of launch_slots that can be resident at once                     CLS_SLOTS_SMALL
+//   uint64_t device_mem_free();                 // bytes of device memory free right now                                  0 (unknown)
+constexpr uint32_t CLS_SLOTS_SMALL = 65536; // lanes of the classification where the larger scratch pools do not fit (the count of rounds 4-11)
+template <class BE> auto classify_lanes(BE& be, int) -> decltype(be.classify_lanes()) { return be.classify_lanes(); }
+template <class BE> uint32_t classify_lanes(BE&, long) { return CLS_SLOTS_SMALL; }
+template <class BE> auto device_mem_free(BE& be, int) -> decltype(be.device_mem_free()) { return be.device_mem_free(); }
+template <class BE> uint64_t device_mem_free(BE&, long) { return 0; }
 template <class BE>
 class Engine {
   public:
@@ -3925,7 +3938,9 @@ class Engine {
 	               uint64_t bulk_calls = 0, bulk_steps = 0, lin_steps = 0, guide_slots = 0, chain_steps = 0, batch_cuts = 0, overflows = 0, memo_hits = 0, memo_adds = 0;
 	               uint64_t tiled_ops = 0, tiled_pending = 0, tile_overflows = 0, cls_covered_reads = 0, archive_bases = 0, cls_decided_reads = 0;
 	               uint64_t lead_stores[2] = { 0, 0 }; // PASS 1, host-check build only: `lead` stores the judges made / left out (TileEnv::lead_stat)
-	               uint64_t commit_rounds_incremental = 0, commit_dirty_records = 0, commit_first_chunk_decided = 0; };
+	               uint64_t commit_rounds_incremental = 0, commit_dirty_records = 0, commit_first_chunk_decided = 0;
+	               double cls_wait_ms = 0;   // PASS 2: host time spent waiting for a classification queued ahead on the side stream (classify_batch)
+	               uint64_t cls_lanes = 0; }; // ... and the lanes the classification runs with (ensure_walk; 0 before the first PASS 2)
 	Stats stats()
 	{
 		Stats s = stats_;
@@ -3938,6 +3953,7 @@ class Engine {
 		}
 		if (arc_.seq && arc_valid_) { uint64_t u = 0; be_.d2h(&u, arc_.used, 8); s.archive_bases = std::min(u, arc_.cap) - ARC_HEAD; }
 		s.guide_slots = guide_slots_;
+		s.cls_lanes = cslots_;
 		return s;
 	}
 
@@ -4745,7 +4761,14 @@ class Engine {
 		if (walk_ready_) return;
 		if (!cend_.hmin) { // (shared by all contexts)
 			p2_batch_ = cfg_.p2_first_batch;
-			cslots_ = std::min<uint32_t>(be_.max_slots(), cfg_.classify_slots);
+			cslots_ = std::min<uint32_t>(be_.max_slots(), cfg_.classify_slots ? cfg_.classify_slots : classify_lanes(be_, 0));
+			if (!cfg_.classify_slots && cslots_ > CLS_SLOTS_SMALL) {
+				// (the wave slots' worth of lanes only where its two scratch pools are small change: at most an eighth of what the
+				// device has free right now -- the walkers' tables, the contig pool and the commit's stamps are yet to come and grow
+				// with the batches.  A backend that cannot tell takes the small count.)
+				const uint64_t pools = 2ull * cslots_ * LA_MAX_VISITED * sizeof(VKey), free_now = device_mem_free(be_, 0);
+				if (pools > free_now / 8) cslots_ = CLS_SLOTS_SMALL;
+			}
 			alloc_tab(cend_, cfg_.cend_log2);
 		}
 		wslots_ = std::min<uint32_t>(be_.max_slots(), cfg_.walk_slots);
@@ -5344,8 +5367,12 @@ class Engine {
 		if (pre_n_ == n && pre_first_ == first) {
 			// classified ahead against an older snapshot (prefetch_classify): BLUNT_END / NOT_SOLID do not
 			// depend on the snapshot and "all k-mers visited" is final once true, so only the candidates
-			// are tested again
+			// are tested again.  (cls_wait_ms: how long the main stream's next launch is held up by that classification -- a host
+			// clock around the wait that was here anyway; what the host queued before it is still running meanwhile, so this is an
+			// upper bound of the device's idle time, and exact once the walkers and their commit are done.)
+			const auto t_wait = std::chrono::steady_clock::now();
 			be_.sync_side();
+			stats_.cls_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wait).count();
 			FRefilter<NW> f{ p_, v, vis_, res_d };
 			be_.launch(n, f, "reclassify");
 		} else if (dist()) {

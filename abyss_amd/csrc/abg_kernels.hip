@@ -4,6 +4,7 @@
 //   k_foreach      one item per lane (hash, claim, insert rounds, classify, predict, ...)
 //   k_foreach_w    the same, launched one wave per workgroup so that the <=32768 walkers
 //                  spread over all 256 CUs (each walker is a latency-bound pointer chase)
+//   k_foreach_wt   the same with the items drawn by ticket, 64 at a draw (the classification)
 //   k_commit       one 256-thread workgroup: the ordered commit, cooperative per contig
 // Launch geometry: wave = 64 lanes, workgroups of 256 (4 waves), grids capped at
 // 256 CUs x 8 workgroups and grid-strided beyond that.
@@ -44,6 +45,24 @@ __global__ void __launch_bounds__(64, ABG_CLS_WAVES) k_foreach_w(F f, uint64_t n
 	const uint32_t slot = (uint32_t)i;
 	for (; i < n; i += stride) f(i, slot);
 }
+// The same with the items drawn by ticket, 64 consecutive ones a draw, as k_walkers draws its candidates: an item of FClassify lasts
+// anything from one table lookup (a read the archive decides) to two look-ahead searches and a sweep, so under a static stride a
+// workgroup dispatched late -- there are more workgroups than wave slots once the walkers hold theirs -- is still working through its
+// share when the others are done.  `slot` (the lane's scratch) is the lane's place in the grid, whatever items it comes to handle.
+template <class F>
+__global__ void __launch_bounds__(64, ABG_CLS_WAVES) k_foreach_wt(F f, uint64_t n, unsigned long long* ticket)
+{
+	const uint32_t slot = blockIdx.x * 64u + threadIdx.x;
+	for (;;) {
+		unsigned long long t = 0;
+		if (threadIdx.x == 0) t = atomicAdd(ticket, 1ull);
+		t = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(t >> 32)) << 32) |
+		    (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)t);
+		if (t * 64 >= n) break;
+		const uint64_t i = t * 64 + threadIdx.x;
+		if (i < n) f(i, slot);
+	}
+}
 
 // One walker per wavefront.  A unitig walk is a long, branchy, dependent chain; 64 of them
 // in one wave would serialise on every divergent branch.  Instead all 64 lanes of a wave
@@ -58,6 +77,12 @@ __global__ void __launch_bounds__(64, ABG_CLS_WAVES) k_foreach_w(F f, uint64_t n
 #ifndef ABG_WALK_LDS
 #define ABG_WALK_LDS 13312 // (160 KB / 12 walkers.  Two per SIMD with 20 KB each -- room for the walkers' neighbour-mask cache --
                            // measured 1.19 s per configs[1] step against 1.16 s for three with less: concurrency wins)
+                           // Four per SIMD (-DABG_WALK_WAVES=4 -DABG_WALK_LDS=10240, 16 walkers a CU), round 12: the kernel takes 128 VGPRs as it
+                           // is, so the code is the same to the instruction -- 819 moves of spilled scalars either way (tools/isa_report.py) -- and
+                           // only the LDS decides; rewalk 157.6-158.2 vs 160.9-163.3 ms, PASS 2 238.4-238.7 vs 241.5-243.2 ms, step 487.0-494.1 vs
+                           // 493.2-497.4 ms over three alternating lines: 3.5 ms of PASS 2, under three times the 1.7 ms spread, and with 10 KB
+                           // of LDS the k = 96 walkers take no chain steps any more (chain_steps 0 in tests/test_gpu_parity.py's k96 case, its
+                           // results unchanged; the other 60 cases pass).  Stays 3.
 #endif
 constexpr uint32_t WALK_LDS = ABG_WALK_LDS;
 template <class F>
@@ -200,6 +225,7 @@ struct HipBackend {
 		if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = (uint32_t)prop.multiProcessorCount;
 		if (hipStreamCreate(&stream) != hipSuccess) { reason = "hipStreamCreate failed"; return; }
 		if (const char* e = getenv("ABG_MEM_LIMIT_MB")) mem_limit = (size_t)strtoull(e, 0, 10) << 20;
+		if (const char* e = getenv("ABG_CLS_TICKETS")) cls_tickets = atoi(e) != 0;
 		{
 			// the side stream only fills gaps: lowest priority (ABG_SIDE_PRIORITY=0 turns that off)
 			int lo = 0, hi = 0;
@@ -215,6 +241,7 @@ struct HipBackend {
 	~HipBackend()
 	{
 		if (ticket) free(ticket);
+		if (cls_ticket_) free(cls_ticket_);
 		if (pin) hipHostFree(pin);
 		for (int i = 0; i < 2; i++) { if (big_pin[i]) hipHostFree(big_pin[i]); if (big_ev[i]) hipEventDestroy(big_ev[i]); }
 		for (int i = 0; i < 2; i++) { if (ahead_pin[i]) hipHostFree(ahead_pin[i]); if (ahead_ev[i]) hipEventDestroy(ahead_ev[i]); if (ahead[i].dev) hipFree(ahead[i].dev); }
@@ -597,7 +624,27 @@ struct HipBackend {
 		uint64_t blocks = (n + 63) / 64;
 		uint64_t cap = slots / 64 ? slots / 64 : 1;
 		if (blocks > cap) blocks = cap;
-		launch_kernel(name, k_foreach_w<F>, dim3((uint32_t)blocks), dim3(64), f, n);
+		if (!cls_tickets) { launch_kernel(name, k_foreach_w<F>, dim3((uint32_t)blocks), dim3(64), f, n); return; }
+		unsigned long long* t = cls_ticket(0);
+		check(hipMemsetAsync(t, 0, 8, stream), "hipMemsetAsync");
+		launch_kernel(name, k_foreach_wt<F>, dim3((uint32_t)blocks), dim3(64), f, n, t);
+	}
+	// the ticket counters of k_foreach_wt: one for the main stream's launches, one for the side stream's (one of each may be pending),
+	// a cache line apart, each cleared on its stream ahead of its launch
+	bool cls_tickets = true; // ABG_CLS_TICKETS=0: the static stride of k_foreach_w (for comparison)
+	unsigned long long* cls_ticket_ = nullptr;
+	unsigned long long* cls_ticket(int side)
+	{
+		if (!cls_ticket_) cls_ticket_ = (unsigned long long*)alloc(256);
+		return cls_ticket_ + (side ? 16 : 0);
+	}
+	uint32_t classify_lanes() const { return cus * 4 * ABG_CLS_WAVES * 64; } // every wave slot k_foreach_w / k_foreach_wt are compiled for
+	uint64_t device_mem_free() const
+	{
+		size_t fr = 0, tot = 0;
+		if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); return 0; }
+		if (mem_limit) fr = std::min(fr, mem_limit > mem_used ? mem_limit - mem_used : (size_t)0);
+		return fr;
 	}
 	// The same on the side stream: it starts after everything queued on the main stream SO FAR
 	// and runs next to whatever the main stream queues afterwards (queue it BEFORE the kernel it
@@ -611,8 +658,11 @@ struct HipBackend {
 		if (blocks > cap) blocks = cap;
 		hipEventRecord(ev2a, stream);              // order after the main stream's queue
 		hipStreamWaitEvent(stream2, ev2a, 0);
+		unsigned long long* t = cls_tickets ? cls_ticket(1) : nullptr;
+		if (t) check(hipMemsetAsync(t, 0, 8, stream2), "hipMemsetAsync");
 		hipEventRecord(ev2a, stream2);
-		hipLaunchKernelGGL(k_foreach_w<F>, dim3((uint32_t)blocks), dim3(64), 0, stream2, f, n);
+		if (t) hipLaunchKernelGGL(k_foreach_wt<F>, dim3((uint32_t)blocks), dim3(64), 0, stream2, f, n, t);
+		else hipLaunchKernelGGL(k_foreach_w<F>, dim3((uint32_t)blocks), dim3(64), 0, stream2, f, n);
 		check(hipGetLastError(), name);
 		hipEventRecord(ev2b, stream2);
 		side_name = name;
@@ -1213,6 +1263,7 @@ int abg_get_stats(const abg_ctx* ctx, abg_stats* out)
 		out->counter_bytes_held = ctx->s.eng->counter_bytes_held();
 		out->commit_rounds_incremental = s.commit_rounds_incremental; out->commit_dirty_records = s.commit_dirty_records;
 		out->commit_first_chunk_decided = s.commit_first_chunk_decided;
+		out->cls_wait_ms = s.cls_wait_ms; out->cls_lanes = s.cls_lanes;
 		return ABG_OK;
 	});
 }

@@ -340,6 +340,8 @@ typedef struct abg_stats {
 	uint64_t commit_rounds_incremental; /* ... of commit_rounds: passes that re-stamped and re-decided only what the pass before had moved */
 	uint64_t commit_dirty_records;      /* contig records whose change of verdict moved a time stamp and so called for another pass, summed over the passes */
 	uint64_t commit_first_chunk_decided; /* parallel commit, plain (not partitioned) runs: contigs and reads whose "every k-mer visited" test failed within its first chunk of k-mers */
+	double cls_wait_ms; /* PASS 2: milliseconds the host waited for a batch's classification, queued ahead on the side stream beside the batch before, before it could go on (0 where nothing is classified ahead) */
+	uint64_t cls_lanes; /* ... lanes the classification kernel runs with: one per wave slot where its scratch fits the free memory, else 65,536; ABG_CLS_SLOTS overrides (0 before the first PASS 2) */
 } abg_stats;
 int abg_get_stats(const abg_ctx* ctx, abg_stats* out);
 
