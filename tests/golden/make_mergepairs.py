@@ -373,6 +373,33 @@ def main():
             inputs = [a for a in argv if a in R.files]
             R.record("error.argv " + " ".join(argv), argv, inputs)
 
+        # ---- sections 11 to 13 draw from a generator of their own, so that nothing above changes when they do
+        rng = random.Random(20261021)
+
+        # ---- 11. the reads the tool is for: 2 x 250 and 2 x 300, fragments from a third of a read to twice a read, 1 to 3 % errors
+        for L in (250, 300):
+            pairs = [fragment_pair(rng, L, L, rng.randint(L // 3, 2 * L), rng.choice((0.01, 0.02, 0.03))) for _ in range(60)]
+            ins = R.put_pairs("eq%d" % L, rng, pairs)
+            R.record("eq%d.default" % L, ins, ins)
+            R.record("eq%d.m3_p0.75" % L, ["-m3", "-p0.75"] + ins, ins)
+
+        # ---- 12. the seams up to the kernel's limit of 512 and past it (513 and 600 are the host's): every pair of these lengths
+        seams = (1, 64, 255, 256, 257, 320, 449, 511, 512, 513, 600)
+        pairs = []
+        for la in seams:
+            for lb in seams:
+                pairs.append(fragment_pair(rng, la, lb, rng.randint(max(la, lb), la + lb), 0.02))
+        ins = R.put_pairs("seam512", rng, pairs)
+        R.record("seam512.default", ins, ins)
+        R.record("seam512.m1_p0.5", ["--matches=1", "--identity=0.5"] + ins, ins)
+        R.record("seam512.m0_p0", ["-m", "0", "-p", "0"] + ins, ins)
+
+        # ---- 13. long pairs that do not overlap: the ties of a last row of 300 to 512 columns
+        pairs = [(dna(rng, rng.randint(300, 512)), dna(rng, rng.randint(300, 512))) for _ in range(60)]
+        ins = R.put_pairs("apart400", rng, pairs)
+        R.record("apart400.default", ins, ins)
+        R.record("apart400.m1_p0", ["-m1", "-p0"] + ins, ins)
+
         files, cases = R.files, R.cases
     mm.OUT = OUT
     mm.write_data(files)

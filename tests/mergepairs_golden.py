@@ -145,6 +145,39 @@ def random_pair(rng: random.Random, la: int, lb: int, alphabet: str = "ACGT", ra
     return noisy(one), reverse_complement(noisy(two))
 
 
+LONG_SETTINGS = ((10, 0.9), (3, 0.75))
+
+
+@functools.lru_cache(maxsize=None)
+def constructed_long_pairs():
+    """Pairs of up to 512 bases whose answer follows from how they are made: (name, read 1, read 2 as the file holds it, index into
+    LONG_SETTINGS, the record's first eight fields there).  Each is one overlap that scores above every other column of the last
+    row, so the reference breaks after it and n_aligned is 1."""
+    rng = random.Random(512)
+    f = random_read(rng, 512)
+    out = [("identical", f, reverse_complement(f), 0, (1, 1, 1, 1, 0, 511, 512, 512))]
+    # the last 5 bases of read 1 are the first 5 of the other: 5 matches are under -m10, so this one is for -m3
+    core = random_read(rng, 5)
+    out.append(("last5", random_read(rng, 507) + core, reverse_complement(core + random_read(rng, 295)), 1, (1, 1, 1, 1, 507, 4, 5, 5)))
+    # read 2 inside read 1, ending where it ends; read 1 inside read 2, starting where it starts
+    g = random_read(rng, 300)
+    out.append(("two_in_one", random_read(rng, 212) + g, reverse_complement(g), 1, (1, 1, 1, 1, 212, 299, 300, 300)))
+    h = random_read(rng, 300)
+    out.append(("one_in_two", h, reverse_complement(h + random_read(rng, 212)), 0, (1, 1, 1, 1, 0, 299, 300, 300)))
+    # One base more in the middle of an overlap of 400.  A gap costs 10,000, so the cell where the overlap would end keeps its
+    # diagonal, half of which is out of step, and no column scores above chance.  The ends are chosen so that chance has one answer:
+    # G against G in column 1 scores 1, and AAAG against GCCC keeps every column of 2 to 8 below that.  The break is taken after
+    # column 1, whose one match -m10 drops: nothing is gapless, where without the inserted base 400 matches would be.
+    c = "GCCC" + random_read(rng, 392) + "AAAG"
+    out.append(("inserted", random_read(rng, 112) + c, reverse_complement(c[:200] + "ACGT"[("ACGT".index(c[200]) + 1) % 4] + c[200:] + random_read(rng, 111)), 0,
+                (1, 0, 0, 0, 0, 0, 0, 0)))
+    # one base against 512: the one cell that starts at column 1 matches, which is fewer matches than -m3 asks for
+    s = random_read(rng, 512)
+    out.append(("512x1", s, reverse_complement(s[-1]), 1, (1, 0, 0, 0, 0, 0, 0, 0)))
+    out.append(("1x512", s[0], reverse_complement(s), 0, (1, 0, 0, 0, 0, 0, 0, 0)))
+    return tuple(out)
+
+
 # ---- the goldens (tests/golden/mergepairs, written by tests/golden/make_mergepairs.py from the unmodified reference)
 
 HERE = os.path.dirname(os.path.abspath(__file__))

@@ -1,7 +1,10 @@
 """abyss-mergepairs without a GPU.  mp_check (mergepairs_core.h over the serial body of abg_mp.h, the text the kernel compiles) must
-write every golden case of tests/golden/mergepairs (from the unmodified reference) byte for byte; the serial body must equal the
-plain-Python restatement of alignOverlap and filterAlignments (tests/mergepairs_golden.py) on random small pairs; the match table
-must equal the restated isMatch on every pair of bytes; and the binary, with no device to be seen, must still write every case that
+write every golden case of tests/golden/mergepairs (from the unmodified reference) byte for byte, among them 2 x 250 and 2 x 300,
+every pair of the lengths 1 to 600 around the kernel's limit of 512 (seam512) and unrelated pairs of 300 to 512 (apart400); the
+serial body must equal the plain-Python restatement of alignOverlap and filterAlignments (tests/mergepairs_golden.py) on random
+pairs of 0 to 14 bases and on 48 pairs of 201 to 512, seven of them constructed so that their record is known; the match table
+must equal the restated isMatch on every pair of bytes, and the identity table the comparison itself up to the 1,024 entries the
+device holds; and the binary, with no device to be seen, must still write every case that
 aligns nothing on the device and say that it has no device where a case does."""
 import functools
 import os
@@ -58,6 +61,21 @@ def test_the_cases_hold_order_dependent_pairs_and_both_ends_of_the_early_break(m
     assert pairs > 1000 and order_dependent >= 20 and taken > 0 and not_taken > 0, total
 
 
+def test_the_long_cases_hold_order_dependent_pairs_too(mp_check, tmp_path):
+    """rows of 250 to 512 columns whose golden outputs came from the reference's std::sort"""
+    total = [0, 0, 0, 0]
+    for name in ("eq250.default", "eq300.default", "seam512.default", "apart400.default"):
+        case = next(c for c in mpg.cases() if c["name"] == name)
+        d = tmp_path / name
+        d.mkdir()
+        counts = d / "counts"
+        mpg.check_case(case, mpg.run_case([mp_check, "run"], case, d, env={"MP_CHECK_COUNTS": str(counts)}))
+        for k, v in enumerate(counts.read_text().split()):
+            total[k] += int(v)
+    pairs, order_dependent, taken, not_taken = total
+    assert pairs == 301 and order_dependent >= 5 and taken > 0 and not_taken > 0, total
+
+
 SETTINGS = ((10, 0.9), (0, 0.0), (1, 0.5), (3, 0.75))
 ALPHABETS = ("ACGT", "AC", "ACGTacgtNn", "ACGTRYKMSWBDHVNacgtrykmswbdhvn")
 
@@ -96,6 +114,52 @@ def test_serial_body_equals_the_restatement(setting, mp_check):
     assert compared > 700
 
 
+LONG_SEAMS = (201, 255, 256, 257, 320, 384, 385, 448, 511, 512)
+
+
+@functools.lru_cache(maxsize=None)
+def long_pairs():
+    """(read 1, read 2, index into mpg.LONG_SETTINGS, the record expected or None): 48 pairs at the lengths the kernel takes and the
+    short test does not reach, the settings dealt out in turn"""
+    rng = random.Random(2)
+    out = []
+    for n in range(35):
+        a, b = mpg.random_pair(rng, rng.choice(LONG_SEAMS), rng.choice(LONG_SEAMS), ALPHABETS[n % len(ALPHABETS)], 0.02)
+        out.append((a, b, n % 2, None))
+    for n in range(6):
+        out.append((mpg.random_read(rng, rng.choice(LONG_SEAMS)), mpg.random_read(rng, rng.choice(LONG_SEAMS)), n % 2, None))
+    out += [(a, b, s, rec) for name, a, b, s, rec in mpg.constructed_long_pairs()]
+    return tuple(out)
+
+
+def test_serial_body_equals_the_restatement_on_long_reads(mp_check):
+    """201 to 512 bases a side: more than 255 matches, paths of 512 cells, starts in the fifth to eighth stripe.  The carried
+    (matches, length, start, fail) against the walk back through the full matrix, which is what takes the time here."""
+    pairs = long_pairs()
+    assert len(pairs) == 48
+    got = []
+    for s, (m, p) in enumerate(mpg.LONG_SETTINGS):
+        text = "".join("%s %s\n" % (a, b) for a, b, at, rec in pairs if at == s)
+        r = subprocess.run([mp_check, "align", str(m), repr(p)], input=text.encode(), stdout=subprocess.PIPE, check=True, timeout=120)
+        got.append(iter([tuple(map(int, line.split())) for line in r.stdout.decode().splitlines()]))
+    compared = 0
+    for a, b, s, expected in pairs:
+        m, p = mpg.LONG_SETTINGS[s]
+        rec = next(got[s])
+        n1, n2, n3, n4, left, order_dependent = mpg.align(a, mpg.reverse_complement(b), m, mpg.float32(p))
+        assert bool(rec[8] & 1) == order_dependent, (a, b)
+        assert not (expected and order_dependent), (a, b)          # every constructed pair is compared
+        if order_dependent:
+            continue
+        assert rec[:4] == (n1, n2, n3, n4), (a, b, rec)
+        assert rec[4:8] == (left if left else (0, 0, 0, 0)), (a, b, rec)
+        if expected:
+            assert rec[:8] == expected, (a, b, rec)
+        compared += 1
+    assert all(next(g, None) is None for g in got)
+    assert compared * 6 >= len(pairs) * 5, compared
+
+
 def test_match_table_is_the_restated_is_match(mp_check):
     r = subprocess.run([mp_check, "table"], stdout=subprocess.PIPE, check=True, timeout=120)
     rows = r.stdout.decode().split()
@@ -111,8 +175,9 @@ def test_match_table_is_the_restated_is_match(mp_check):
 
 def test_identity_table_is_the_comparison_itself(mp_check):
     for p in (0.9, 0.5, 0.75, 0.3, 0.0, 1.0):
-        r = subprocess.run([mp_check, "identity", repr(p), "300"], stdout=subprocess.PIPE, check=True, timeout=120)
+        r = subprocess.run([mp_check, "identity", repr(p), "1024"], stdout=subprocess.PIPE, check=True, timeout=120)   # the device's table
         table = [int(x) for x in r.stdout.split()]
+        assert len(table) == 1024
         f = mpg.float32(p)
         for L, least in enumerate(table, 1):
             assert all((m / L < f) == (m < least) for m in range(L + 1)), (p, L, least)
